@@ -17,9 +17,17 @@ order, so the tracker state carries across steps exactly as in rgbd_mmt.  By def
 results are deferred (mmt_set_deferred_objects): the object pipeline keeps running across steps
 instead of draining at every chunk boundary, each frame's object motions arrive with a later
 step's results, and the timed region ends with mmt_flush_objects, so every timed frame's objects
-are computed inside it (--immediate: drain at every step).  `one_frame_per_call` times the
-reference-shaped call pattern (one frame per mmt_track_rgbd_chunk_device call, deferred objects)
-on the frames after the timed region.
+are computed inside it (--immediate: drain at every step).
+
+A plain run renders the sequence, warms up, times --steps steps and prints the line: value,
+ms_per_step (the timed region over the timed steps that ran), the validity and map counters of
+the timed frames and the roofline record, which all come from the timed steps themselves.
+--dump-outputs DIR also writes what the last timed step gave its caller (dump_outputs) as
+DIR/<name>.npy; the sequence depends on the arguments alone, so two builds can be compared array
+for array.  Everything that takes runs of its own is behind --full: `one_frame_per_call` (the
+reference-shaped call pattern, one frame per mmt_track_rgbd_chunk_device call, deferred objects,
+on the frames after the timed region), the C2 leg, the CPU legs below (cpu_baseline, parity) and
+rank_parity; a plain line holds null for them.
 
 Multi-GPU: one process per GPU, independent sequences, no data-path collective; barrier + device
 sync bracket the timed region; time = MAX over ranks; value = frames of all ranks / that time
@@ -34,8 +42,8 @@ with SURVEY 8(d)'s B_orb = 3WH + 4P + 60N plus A2's 6WH algorithmic bytes per fr
 launch, over its average duration from HIP events the library records on the launch stream around
 every window (mmt_profile_*), vs the 8 TB/s HBM peak.
 
-cpu_baseline (rank 0, N = 1 only): the CPU oracle tracker (oracle/track_ref.cpp, a scalar C++
-restatement of the reference's per-frame path) on one pinned core.  It tracks the same sequence
+cpu_baseline (--full; rank 0, N = 1 only): the CPU oracle tracker (oracle/track_ref.cpp, a scalar
+C++ restatement of the reference's per-frame path) on one pinned core.  It tracks the same sequence
 from frame 0 (the chain has to be replayed), is timed on the frame range the GPU timed region
 starts with, and every frame it tracks is compared with the GPU's result for that frame (the
 "parity" record).  --cpu-seqs K adds K independent sequences on K pinned cores (BASELINE C4/C5
@@ -150,6 +158,15 @@ def parse_args(argv=None):
     ap.add_argument("--rank-parity-frames", type=int, default=192,
                     help="frames of every sequence checked against the oracle on lines with "
                          "several sequences or ranks (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the headline figure: "
+                         "the CPU oracle (cpu_baseline, parity; --no-cpu, --cpu-seconds, "
+                         "--cpu-seqs), the C2 leg (--c2-steps), the one-frame-per-call leg "
+                         "(--single-frames) and rank_parity (--rank-parity-frames); without it "
+                         "those records are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (poses, counts, "
+                         "object motions of its frames) as DIR/<name>.npy")
     ap.add_argument("--dry", action="store_true", help="CPU rehearsal of the rank logic")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic.json"))
     return ap.parse_args(argv)
@@ -204,6 +221,43 @@ def seq_frame_numpy(seq, i):
     """Host copy of frame i of a device-resident sequence (oracle input layout)."""
     from multimot_track_amd import scene
     return scene.to_numpy_frames({k: seq[k][i:i + 1] for k in ("bgr", "disp", "flow", "mask")})[0]
+
+
+FRAME_STATS = ("frame_index", "initialized", "n_keys", "n_obj_samples", "ego_iterations",
+               "ego_inliers", "map_state", "map_matches_mm", "map_inliers_local", "n_keyframes",
+               "n_mappoints", "new_keyframe")
+OBJECT_STATS = ("label", "sem_label", "n_points", "n_inliers", "ransac_inliers", "mm_inliers",
+                "n_solve", "iterations")
+
+
+def dump_outputs(path, frames, prefix=""):
+    """--dump-outputs: the per-frame results of one step as a caller of the timed path holds them
+    (mmt_track_rgbd_chunk_device's MmtFrameResult per frame, each frame's own object motions from
+    that call, a later one or mmt_flush_objects), one array per field group with the frame as the
+    first axis.  Poses and motions stay float32 as the C-ABI returns them; the integer fields go
+    to float64 columns in the order of FRAME_STATS / OBJECT_STATS (plus the object count);
+    object slots past a frame's count are zero."""
+    import multimot_track_amd as M
+    n, mo = len(frames), M.MAX_OBJECTS
+    out = {"Tcw": np.stack([d["Tcw"] for d in frames]).astype(np.float32),
+           "Tcw_map": np.stack([d["Tcw_map"] for d in frames]).astype(np.float32),
+           "frame_stats": np.array([[float(d[k]) for k in FRAME_STATS] + [float(len(d["objects"]))]
+                                    for d in frames], np.float64),
+           "object_stats": np.zeros((n, mo, len(OBJECT_STATS)), np.float64),
+           "object_motion": np.zeros((n, mo, 4, 4), np.float32),
+           "object_cam_pose": np.zeros((n, mo, 4, 4), np.float32),
+           "object_init_pose": np.zeros((n, mo, 4, 4), np.float32),
+           "object_centre_pre": np.zeros((n, mo, 3), np.float32)}
+    for i, d in enumerate(frames):
+        for j, o in enumerate(d["objects"][:mo]):
+            out["object_stats"][i, j] = [float(o[k]) for k in OBJECT_STATS]
+            out["object_motion"][i, j] = o["motion"]
+            out["object_cam_pose"][i, j] = o["X"]
+            out["object_init_pose"][i, j] = o["init"]
+            out["object_centre_pre"][i, j] = o["centre_pre"]
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, prefix + name + ".npy"), a)
 
 
 # ------------------------------------------------------------------ CPU legs (rank 0, N = 1)
@@ -365,6 +419,7 @@ def run_dry(args, rank, world):
     shard.barrier(world, dev)
     elapsed = shard.max_over_ranks(time.perf_counter() - t0, world, dev)
     frames_all = shard.sum_over_ranks(sum(t for _, t in rsteps) * C, world, dev)
+    steps_run = int(shard.max_over_ranks(max(t for _, t in rsteps), world, dev))
     mine = [dict(name=wl["name"], seed=wl["seed"], width=wl["width"], height=wl["height"],
                  timed_steps=t) for wl, (_, t) in zip(wls, rsteps)]
     all_seeds = [None] * world
@@ -378,7 +433,8 @@ def run_dry(args, rank, world):
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": round(frames_all / elapsed, 2),
                           "unit": "frames/s", "n_gpus": world // R, "steps": args.steps,
-                          "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+                          "warmup": args.warmup,
+                          "ms_per_step": round(elapsed / max(steps_run, 1) * 1e3, 4),
                           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                           "dtype": "u8", "data": "dry run (no GPU work)",
                           "config": {"workload": "dry", "config": args.config,
@@ -514,11 +570,18 @@ def main(argv=None):
     prof = ctx.profile_read()
     elapsed = shard.max_over_ranks(elapsed, world, rdev)
     frames_all = shard.sum_over_ranks(sum(t for _, t in rsteps) * C, world, rdev)
+    # the timed steps that ran: --steps, or fewer where every C4 sequence ends before them
+    steps_run = int(shard.max_over_ranks(max(t for _, t in rsteps), world, rdev))
 
     # per-frame outputs of every sequence (sanity: every timed frame tracked by the map, objects
     # found); a line whose timed frames are not all tracked is marked invalid
     seq_frames = [assemble([r[k] for r in warm + results if k in r], C, flushed[k])
                   for k in range(K)]
+    if args.dump_outputs:  # the last timed step of every sequence of this rank
+        for k, f in enumerate(seq_frames):
+            if rsteps[k][1] > 0:
+                dump_outputs(args.dump_outputs, f[-C:],
+                             "" if rank == 0 and k == 0 else "rank%d_seq%d_" % (rank, k))
     all_frames = seq_frames[0]
     timed_frames = all_frames[rsteps[0][0] * C:]
     n_obj_last = len(timed_frames[-1]["objects"]) if timed_frames else 0
@@ -558,7 +621,7 @@ def main(argv=None):
     # every rank's sequences checked against the oracle over their first frames (several sequences
     # or ranks: the N = 1 line's CPU leg below checks the one sequence over more frames)
     rank_par = None
-    if (world > 1 or K > 1) and args.rank_parity_frames > 0:
+    if args.full and (world > 1 or K > 1) and args.rank_parity_frames > 0:
         rank_par = rank_parity(args, seqs, seq_frames, rank, wls)
         if world > 1:
             gathered = [None] * world
@@ -573,7 +636,8 @@ def main(argv=None):
         key = "%dx%d_n%d_b%d" % (W, H, NF, C)
         traffic = load_traffic(args.traffic_file, key)
         cpu, parity, c2, single = None, None, None, None
-        if world == 1 and args.single_frames > 0 and args.config == "C3":
+        solo = args.full and world == 1  # the legs of --full on an N = 1 line
+        if solo and args.single_frames > 0 and args.config == "C3":
             # the reference-shaped call pattern: one frame per call (rgbd_tum.cc's loop), objects
             # deferred; a fresh sequence context over the frames after the timed region
             ns = args.single_frames
@@ -602,7 +666,7 @@ def main(argv=None):
                                 "flush inside the timed region" % (7 + ns)}
             sctx.close()
             del s1
-        if world == 1 and args.c2_steps > 0 and args.config == "C3":
+        if solo and args.c2_steps > 0 and args.config == "C3":
             # C2 (ego only): same camera and sequence seed, mask == 0
             nc2 = (1 + args.c2_steps) * C
             s2 = render(shard.sequence_seed(1003, 0), nc2, objects=0)
@@ -619,7 +683,7 @@ def main(argv=None):
             c2 = {"value": round(args.c2_steps * C / t2, 2), "unit": "frames/s",
                   "frames": args.c2_steps * C, "timed_from": C}
             c2ctx.close()
-        if world == 1 and not args.no_cpu:
+        if solo and not args.no_cpu:
             gpu_frames = all_frames
             timed_from = rsteps[0][0] * C
             n_t, t_t, parity = cpu_leg(args, seq, gpu_frames, timed_from, W, H, NF)
@@ -655,7 +719,7 @@ def main(argv=None):
             "frames_timed": frames_timed, "frames_tracked": tracked,
             "valid": tracked == frames_timed,
             "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "ms_per_step": round(elapsed / max(steps_run, 1) * 1e3, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u8", "data": "synthetic (seeded ray-cast street sequence, exact depth/flow/"
                                    "labels, KITTI-03 camera), resident in HBM",

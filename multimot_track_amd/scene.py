@@ -250,15 +250,137 @@ class SequenceRenderer:
         mask = torch.where(sid >= 10, sid - 9, torch.zeros_like(sid)).to(torch.int32)
         return bgr, disp, flow, mask
 
-    def sequence(self, nframes, start=0):
+    def frames(self, ts):
+        """frame(t) of every t in ts, stacked: the same arithmetic element for element, so the
+        arrays equal frame()'s bit for bit (tests/test_scene.py).  frame() issues some 4,000
+        small launches per frame and is bound by them; here every elementwise operation runs
+        once over all the frames, and the textures are evaluated only at the pixels that show
+        their surface.  The 3x3 matrix products stay one per frame with frame()'s shapes, so no
+        other GEMM kernel (and summation order) is picked."""
+        sc, dev, H, W = self.scene, self.dev, self.H, self.W
+        B, nobj = len(ts), len(sc.objs)
+        f64 = torch.float64
+
+        def col3(v):  # [B, 3] -> broadcast over the pixels
+            return v[:, None, None, :]
+
+        def col1(v):  # [B] -> broadcast over the pixels
+            return v[:, None, None]
+        Twc = self._t(np.stack([sc.Twc(t) for t in ts]))
+        Two0 = [self._t(np.stack([sc.Two(k, t) for t in ts])) for k in range(nobj)]
+        Two1 = [self._t(np.stack([sc.Two(k, t + 1) for t in ts])) for k in range(nobj)]
+        Tcw1 = self._t(np.stack([np.linalg.inv(sc.Twc(t + 1)) for t in ts]))
+        # ---- _cast
+        o = Twc[:, :3, 3]
+        dw = torch.stack([self.ray @ Twc[b, :3, :3].T for b in range(B)])
+        inf = torch.full((B, H, W), float("inf"), dtype=f64, device=dev)
+        Z = inf.clone()
+        sid = torch.zeros(B, H, W, dtype=torch.int32, device=dev)
+        dy, dx = dw[..., 1], dw[..., 0]
+        zg = torch.where(dy > 1e-9, (CAM_HEIGHT - col1(o[:, 1])) / dy, inf)
+        take = zg < Z
+        Z = torch.where(take, zg, Z)
+        sid = torch.where(take, torch.full_like(sid, 1), sid)
+        for wall_x, code, sgn in ((WALL_L, 2, -1.0), (WALL_R, 3, 1.0)):
+            zw = torch.where(sgn * dx > 1e-9, (wall_x - col1(o[:, 0])) / dx, inf)
+            yw = col1(o[:, 1]) + zw * dy
+            zw = torch.where((yw > WALL_TOP) & (yw < CAM_HEIGHT), zw, inf)
+            take = zw < Z
+            Z = torch.where(take, zw, Z)
+            sid = torch.where(take, torch.full_like(sid, code), sid)
+        e = self._t(BOX_HALF)
+        for k in range(nobj):
+            Two = Two0[k]
+            oo = torch.stack([Two[b, :3, :3].T @ (o[b] - Two[b, :3, 3]) for b in range(B)])
+            do = torch.stack([dw[b] @ Two[b, :3, :3] for b in range(B)])
+            inv = 1.0 / torch.where(do.abs() < 1e-12, torch.full_like(do, 1e-12), do)
+            t1 = col3(-e - oo) * inv
+            t2 = col3(e - oo) * inv
+            tn = torch.minimum(t1, t2).amax(-1)
+            tf = torch.maximum(t1, t2).amin(-1)
+            del do, inv, t1, t2
+            zb = torch.where((tn <= tf) & (tn > 0.1), tn, inf)
+            take = zb < Z
+            Z = torch.where(take, zb, Z)
+            sid = torch.where(take, torch.full_like(sid, 10 + k), sid)
+        Pw = col3(o) + Z.unsqueeze(-1).clamp(max=1e6) * dw
+        del dw, dy, dx
+        # ---- _colour, and the boxes' next positions for the flow
+        g = torch.full((B, H, W), 200.0, dtype=f64, device=dev).to(torch.float32)
+        tint = torch.zeros(B, H, W, 3, dtype=torch.float32, device=dev)
+        P32 = Pw.to(torch.float32)
+        seed = sc.seed
+        for code, a, b_, salt, col in ((1, 0, 2, seed * 7 + 1, (0.95, 1.0, 1.05)),
+                                       (2, 2, 1, seed * 7 + 2, (1.1, 1.0, 0.9)),
+                                       (3, 2, 1, seed * 7 + 3, (0.9, 1.0, 1.1))):
+            m = sid == code
+            Pm = P32[m]
+            g[m] = _texture(Pm[:, a], Pm[:, b_], salt)
+            tint[m] = torch.tensor(col, device=dev)
+        del P32
+        Pn = Pw.clone()
+        for k in range(nobj):
+            m = sid == 10 + k
+            seen = m.flatten(1).any(1).tolist()
+            if not any(seen):
+                continue
+            T0, T1 = Two0[k], Two1[k]
+            Pl32 = torch.zeros(B, H, W, 3, dtype=torch.float32, device=dev)
+            for b in range(B):
+                if not seen[b]:
+                    continue
+                Pl = (Pw[b] - T0[b, :3, 3]) @ T0[b, :3, :3]
+                Pl32[b] = Pl.to(torch.float32)
+                Pn[b] = torch.where(m[b].unsqueeze(-1), Pl @ T1[b, :3, :3].T + T1[b, :3, 3],
+                                    Pn[b])
+            Pl = Pl32[m]
+            del Pl32
+            ax = (Pl / torch.tensor(BOX_HALF, device=dev)).abs().argmax(-1)
+            s = torch.where(ax == 0, Pl[:, 2], Pl[:, 0])
+            tt = torch.where(ax == 1, Pl[:, 2], Pl[:, 1])
+            g[m] = _texture(s + 13.0 * k, tt, seed * 7 + 100 + k)
+            col = (1.0 + 0.15 * math.sin(k), 1.0, 1.0 - 0.15 * math.cos(k))
+            tint[m] = torch.tensor(col, device=dev)
+        tint[sid == 0] = torch.tensor((1.05, 1.0, 0.95), device=dev)
+        bgr = torch.clamp(g.unsqueeze(-1) * tint + 0.5, 0, 255).to(torch.uint8)
+        del g, tint
+        # ---- disparity
+        valid = torch.isfinite(Z) & (Z > 0.1)
+        dq = torch.where(valid, torch.round(256.0 * self.K["bf"] / Z.clamp(min=0.1)),
+                         torch.zeros_like(Z))
+        dq = torch.where(dq <= 65535, dq, torch.zeros_like(dq))
+        disp = dq.to(torch.int32).to(torch.int16)
+        # ---- forward flow
+        pc = torch.stack([Pn[b] @ Tcw1[b, :3, :3].T + Tcw1[b, :3, 3] for b in range(B)])
+        del Pn, Pw
+        z = pc[..., 2]
+        u1 = pc[..., 0] / z * self.K["fx"] + self.K["cx"]
+        v1 = pc[..., 1] / z * self.K["fy"] + self.K["cy"]
+        fu = torch.where(valid, u1 - self.u, torch.zeros_like(u1))
+        fv = torch.where(valid, v1 - self.v, torch.zeros_like(v1))
+        flow = torch.stack([fu, fv], -1).to(torch.float32)
+        mask = torch.where(sid >= 10, sid - 9, torch.zeros_like(sid)).to(torch.int32)
+        return bgr, disp, flow, mask
+
+    def sequence(self, nframes, start=0, batch=None):
+        """Frames start .. start + nframes - 1, `batch` at a time through frames() (default: 32
+        on a GPU, 4 on the host; aa > 1 goes frame by frame)."""
         F, H, W = nframes, self.H, self.W
         out = dict(bgr=torch.empty(F, H, W, 3, dtype=torch.uint8, device=self.dev),
                    disp=torch.empty(F, H, W, dtype=torch.int16, device=self.dev),
                    flow=torch.empty(F, H, W, 2, dtype=torch.float32, device=self.dev),
                    mask=torch.empty(F, H, W, dtype=torch.int32, device=self.dev))
-        for i in range(F):
-            b, d, f, m = self.frame(start + i)
-            out["bgr"][i], out["disp"][i], out["flow"][i], out["mask"][i] = b, d, f, m
+        if batch is None:
+            batch = 32 if self.dev.type == "cuda" else 4
+        for i in range(0, F, batch):
+            n = min(batch, F - i)
+            if self.aa > 1:
+                b, d, f, m = (torch.stack(x) for x in zip(*[self.frame(start + i + j)
+                                                            for j in range(n)]))
+            else:
+                b, d, f, m = self.frames([start + i + j for j in range(n)])
+            out["bgr"][i:i + n], out["disp"][i:i + n] = b, d
+            out["flow"][i:i + n], out["mask"][i:i + n] = f, m
         out["Tcw"] = np.stack([np.linalg.inv(self.scene.Twc(start + i)) for i in range(F)])
         return out
 

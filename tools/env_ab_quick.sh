@@ -2,16 +2,17 @@
 # Usage: env_ab_quick.sh <tag> [VAR=value ...]   (VAR=value,VAR2=value2 sets several)
 set -e
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
-mkdir -p gpurun_out
+OUT=${MMT_OUT:-bench_out}
+mkdir -p $OUT
 export TMPDIR=/tmp
 tag=$1; shift
 i=0
 for v in default "$@"; do
-  out=gpurun_out/abq_${tag}_$i
+  out=$OUT/abq_${tag}_$i
   if [ "$v" = default ]; then
-    timeout -k 10 300 python bench.py --no-cpu > $out.json 2> $out.err
+    timeout -k 10 300 python bench.py --full --no-cpu > $out.json 2> $out.err
   else
-    env ${v//,/ } timeout -k 10 300 python bench.py --no-cpu > $out.json 2> $out.err
+    env ${v//,/ } timeout -k 10 300 python bench.py --full --no-cpu > $out.json 2> $out.err
   fi
   echo "$v: $(python -c "import json;d=json.load(open('$out.json'));print(d['value'], d['config']['c2']['value'])")"
   i=$((i+1))
