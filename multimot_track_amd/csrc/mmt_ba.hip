@@ -268,7 +268,8 @@ namespace {
 // (10-11 ms per local BA of the C3 sequence); spread, a trial costs a few microseconds per kernel.
 //   per iteration (need_lin):  k_ba2_lin   one thread per point: errors, robust chi2, H_ll, b_l,
 //                                          H_pl and the edge's pose terms (J_p^T w J_p, J_p^T w e)
-//                              k_ba2_kfsum one workgroup per optimised keyframe: H_pp, b_p
+//                              k_ba2_kfsum one workgroup per optimised keyframe: H_pp, b_p; one
+//                                          per 256 points: k_ba2_lin's chi2 and diagonal partials
 //   per trial:                 k_ba2_p1    one thread per point: (H_ll + lambda I)^-1, Y, H_pl D^-1 b_l
 //                              k_ba2_p2    one workgroup per keyframe-pair block / keyframe: Schur sums
 //                              k_ba2_p3    one workgroup: the reduced system, LDL^T, increments, trial poses
@@ -276,6 +277,8 @@ namespace {
 //                                          its last workgroup then takes the LM decision (rho,
 //                                          lambda, Raul's stop, the chi2-increase stop) and the
 //                                          iteration and round bookkeeping (ba2_decide)
+// ("One thread per point": a point with more than kBaHeavy edges gets a wave instead, in the
+// workgroups that follow the thread-per-point ones in the same grid.)
 // The estimates are double-buffered (current / trial, swapped on acceptance), so a rejected trial
 // needs no restore.  Every reduction has a fixed order: the solve is deterministic.
 
@@ -283,6 +286,16 @@ constexpr int kMkThreads = 256;
 constexpr int kMkWaves = kMkThreads / 64;
 constexpr int kMkSolveThreads = 512;
 constexpr int kMkDecideThreads = 1024;
+// The point kernels' workgroup (k_ba2_lin, k_ba2_p1, k_ba2_p4): a thread per light point, then a
+// wave per heavy point.  They hold no workgroup-level sum (the partials linpart / p4part are
+// rebuilt from the per-point array pres over kMkThreads consecutive points each, whatever this
+// size), so the size is a pure speed choice.
+#ifndef MMT_BA_PT_THREADS
+#define MMT_BA_PT_THREADS 256  // A/B builds: tools/ab_build.sh <tag> --src mmt_ba.hip -DMMT_BA_PT_THREADS=64
+#endif
+constexpr int kPtThreads = MMT_BA_PT_THREADS;
+constexpr int kPtWaves = kPtThreads / 64;
+static_assert(kPtThreads % 64 == 0 && kPtThreads >= 64 && kPtThreads <= 1024, "whole waves");
 
 struct BAState {
   int done, round, iter, qmax, need_lin, lam_init, cb, ok2, nBad, nact;
@@ -320,18 +333,20 @@ struct BAWork2 {
   double* Hpart;    // 27 per keyframe item: its edges' pose terms
   double* Spart;    // 36 per block item: its triples' sum of Y H_pl^T
   double* cvpart;   // 6 per keyframe item: its edges' H_pl D^-1 b_l
-  double* linpart;  // 2 per point workgroup: chi2, largest active H_ll diagonal
-  double* p4part;   // 2 per point workgroup: trial chi2, scale
+  double* linpart;  // 2 per kMkThreads points: chi2, largest active H_ll diagonal (k_ba2_kfsum)
+  double* p4part;   // 2 per kMkThreads points: trial chi2, scale (k_ba2_p4's last workgroup)
   unsigned* p4cnt;  // k_ba2_p4's workgroups done with the trial (the last one decides, then resets)
   uint8_t* level;   // n_edge
   int* eopt;        // n_edge: the edge's optimised-keyframe index, -1 for a fixed keyframe
   uint8_t* kf_act;  // n_kf: optimised keyframe with an active edge this round
   uint8_t* pt_act;  // n_pt
-  int gP;           // partial sums: one per point workgroup
-  int gPp;          // point workgroups (one thread per point; k_ba2_p1's heavy waves follow them)
+  int gP;           // partial sums: one per kMkThreads consecutive points
+  int gPp;          // light point workgroups (kPtThreads points, a thread each; the heavy points'
+                    // workgroups follow them in the grids of k_ba2_lin, k_ba2_p1 and k_ba2_p4)
   const int* heavy; // the points with more than kBaHeavy edges, one wave each
   int n_heavy;
-  double* hres;     // 2 n_pt: a heavy point's (chi2, H_ll diagonal max) or (trial chi2, scale)
+  double* pres;     // 2 n_pt: every point's (chi2, H_ll diagonal max) after k_ba2_lin, its
+                    // (trial chi2, scale) after k_ba2_p4
   int spec;         // k_ba2_p4<true>: the trial kernel linearises at the trial state
 };
 
@@ -639,72 +654,74 @@ __device__ __forceinline__ double ba2_lin_point_wave(const BADesc& d, const BAWo
   return sum[0];
 }
 
-// the linearisation at the current estimate, one thread per point (the start of each round, and an
-// iteration that follows a rejected trial; after an accepted one k_ba2_p4 has linearised already)
-__global__ __launch_bounds__(kMkThreads) void k_ba2_lin(BADesc d, BAWork2 w) {
-  __shared__ double s_part[2 * kMkWaves];
+// the linearisation at the current estimate (the start of each round, and an iteration that
+// follows a rejected trial; after an accepted one k_ba2_p4 has linearised already): the first gPp
+// workgroups take the light points, a thread each, the others the heavy points, a wave each (the
+// two touch disjoint points and edges).  Every point leaves its (chi2, largest H_ll diagonal) in
+// pres; no workgroup adds anything up here: k_ba2_kfsum's extra workgroups build linpart from pres
+// in the order the one-thread-per-point kernel added them (the launch boundary is the reduce's
+// barrier, and that launch exists anyway).
+__global__ __launch_bounds__(kPtThreads) void k_ba2_lin(BADesc d, BAWork2 w) {
+  __shared__ double s_stage[kPtWaves][64 * 13];
   const BAState* st = w.st;
   if (st->done || !st->need_lin || st->spec_ok) return;
   const bool robust = st->round == 0;
   const int cb = st->cb;
   const DSE3* pose = w.pose + (size_t)cb * d.n_kf;
   const double* Xc = w.X + (size_t)cb * 3 * d.n_pt;
-  const int j = blockIdx.x * kMkThreads + threadIdx.x;
-  double chi = 0, mx = 0;
-  if (j < d.n_pt) {
-    double m = 0;
-    if (ba2_heavy(d, j)) {  // linearised by its wave in k_ba2_lin_heavy: its results
-      chi = w.hres[2 * (size_t)j];
-      m = w.hres[2 * (size_t)j + 1];
-    } else {
-      const double X[3] = {Xc[3 * (size_t)j], Xc[3 * (size_t)j + 1], Xc[3 * (size_t)j + 2]};
-      chi = ba2_lin_point(d, w, j, pose, X, robust, cb, &m);
-    }
-    if (w.pt_act[j]) mx = m;
-  }
-  const double cs = wave_sum_dpp(chi);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) s_part[wave] = cs;
-  const double m = wg_maxN<kMkWaves>(mx, s_part + kMkWaves);  // its barrier orders s_part too
-  if (threadIdx.x == 0) {
-    double t = 0;
-#pragma unroll
-    for (int q = 0; q < kMkWaves; q++) t += s_part[q];
-    w.linpart[2 * blockIdx.x] = t;
-    w.linpart[2 * blockIdx.x + 1] = m;
-  }
-}
-
-// the heavy points' linearisation, a wave each, before k_ba2_lin (which takes their chi2 and
-// H_ll diagonal maximum from hres into its sums at the point's own place: the sums' order is the
-// one-thread-per-point kernel's)
-__global__ __launch_bounds__(kMkThreads) void k_ba2_lin_heavy(BADesc d, BAWork2 w) {
-  __shared__ double s_stage[kMkWaves][64 * 13];
-  const BAState* st = w.st;
-  if (st->done || !st->need_lin || st->spec_ok) return;
+  const bool heavy_wg = (int)blockIdx.x >= w.gPp;
   const int wave = threadIdx.x >> 6;
-  const int hi = (int)blockIdx.x * kMkWaves + wave;
-  if (hi >= w.n_heavy) return;
-  const int cb = st->cb;
-  const DSE3* pose = w.pose + (size_t)cb * d.n_kf;
-  const double* Xc = w.X + (size_t)cb * 3 * d.n_pt;
-  const int j = w.heavy[hi];
+  int j = blockIdx.x * kPtThreads + threadIdx.x;
+  if (heavy_wg) {
+    const int hi = ((int)blockIdx.x - w.gPp) * kPtWaves + wave;
+    if (hi >= w.n_heavy) return;
+    j = w.heavy[hi];
+  } else if (j >= d.n_pt || ba2_heavy(d, j)) {
+    return;
+  }
   const double X[3] = {Xc[3 * (size_t)j], Xc[3 * (size_t)j + 1], Xc[3 * (size_t)j + 2]};
   double m = 0;
-  const double c = ba2_lin_point_wave(d, w, j, pose, X, st->round == 0, cb, &m, s_stage[wave]);
-  if ((threadIdx.x & 63) == 0) {
-    w.hres[2 * (size_t)j] = c;
-    w.hres[2 * (size_t)j + 1] = m;
+  const double c = heavy_wg ? ba2_lin_point_wave(d, w, j, pose, X, robust, cb, &m, s_stage[wave])
+                            : ba2_lin_point(d, w, j, pose, X, robust, cb, &m);
+  if (!heavy_wg || (threadIdx.x & 63) == 0) {
+    w.pres[2 * (size_t)j] = c;
+    w.pres[2 * (size_t)j + 1] = m;
   }
 }
 
 // buildSystem's keyframe side: one workgroup per keyframe item (<= 256 edges of one optimised
-// keyframe, one per thread) sums its active edges' pose terms into Hpart
+// keyframe, one per thread) sums its active edges' pose terms into Hpart.  gP more workgroups
+// follow them: workgroup g of these adds up points kMkThreads g .. kMkThreads (g + 1) - 1 of
+// k_ba2_lin's per-point results into linpart[2 g] (chi2: thread <-> point, DPP wave sums over 64
+// consecutive points, the wave sums added in order) and linpart[2 g + 1] (the largest H_ll diagonal
+// of an active point); they run exactly when k_ba2_lin ran.
 __global__ __launch_bounds__(kMkThreads) void k_ba2_kfsum(BADesc d, BAWork2 w) {
   __shared__ double s_part[27 * kMkWaves];
   __shared__ double s_out[32];
   const BAState* st = w.st;
   if (st->done || !st->need_lin) return;
+  if ((int)blockIdx.x >= w.n_kitem) {
+    if (st->spec_ok) return;
+    const int g = (int)blockIdx.x - w.n_kitem;
+    const int j = g * kMkThreads + threadIdx.x;
+    double chi = 0, mx = 0;
+    if (j < d.n_pt) {
+      chi = w.pres[2 * (size_t)j];
+      if (w.pt_act[j]) mx = w.pres[2 * (size_t)j + 1];
+    }
+    const double cs = wave_sum_dpp(chi);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) s_part[wave] = cs;
+    const double m = wg_maxN<kMkWaves>(mx, s_part + kMkWaves);  // its barrier orders s_part too
+    if (threadIdx.x == 0) {
+      double t = 0;
+#pragma unroll
+      for (int q = 0; q < kMkWaves; q++) t += s_part[q];
+      w.linpart[2 * g] = t;
+      w.linpart[2 * g + 1] = m;
+    }
+    return;
+  }
   const int4 it = w.kitem[blockIdx.x];
   const int t = it.y + threadIdx.x;
   double acc[27];
@@ -724,16 +741,16 @@ __global__ __launch_bounds__(kMkThreads) void k_ba2_kfsum(BADesc d, BAWork2 w) {
 
 // trial step 1, one thread per active point: D^-1 = (H_ll + lambda I)^-1 (Eigen's cofactor
 // inverse), and per active edge to an optimised keyframe Y = H_pl D^-1 and H_pl D^-1 b_l
-__global__ __launch_bounds__(kMkThreads) void k_ba2_p1(BADesc d, BAWork2 w) {
+__global__ __launch_bounds__(kPtThreads) void k_ba2_p1(BADesc d, BAWork2 w) {
   const BAState* st = w.st;
   if (st->done) return;
   __shared__ double s_lam;
   const double lambda = st->lam_init ? ba2_lambda_init(d, w, &s_lam) : st->lambda;
   const bool heavy_wg = (int)blockIdx.x >= w.gPp;
   const int lane = threadIdx.x & 63;
-  int j = blockIdx.x * kMkThreads + threadIdx.x;
+  int j = blockIdx.x * kPtThreads + threadIdx.x;
   if (heavy_wg) {  // a wave per heavy point, lanes over its edges (each edge's Y and cv alone)
-    const int hi = ((int)blockIdx.x - w.gPp) * kMkWaves + (int)(threadIdx.x >> 6);
+    const int hi = ((int)blockIdx.x - w.gPp) * kPtWaves + (int)(threadIdx.x >> 6);
     j = hi < w.n_heavy ? w.heavy[hi] : d.n_pt;
   } else if (j < d.n_pt && ba2_heavy(d, j)) {
     return;
@@ -1330,67 +1347,94 @@ __device__ __forceinline__ void ba2_trial_point(const BADesc& d, const BAWork2& 
   *sc_out = sc;
 }
 
-// the heavy points' trials, a wave each, before k_ba2_p4 (which adds their chi2 and scale terms
-// from hres at the point's own place)
-__global__ __launch_bounds__(kMkThreads) void k_ba2_p4_heavy(BADesc d, BAWork2 w) {
-  __shared__ double s_stage[kMkWaves][64];
-  if (w.st->done) return;
-  const int wave = threadIdx.x >> 6;
-  const int hi = (int)blockIdx.x * kMkWaves + wave;
-  if (hi >= w.n_heavy) return;
-  const int j = w.heavy[hi];
-  double chi, sc;
-  ba2_trial_point<true>(d, w, j, s_stage[wave], &chi, &sc);
-  if ((threadIdx.x & 63) == 0) {
-    w.hres[2 * (size_t)j] = chi;
-    w.hres[2 * (size_t)j + 1] = sc;
+// p4part from the per-point (trial chi2, scale) in pres, by every wave of the deciding workgroup:
+// p4part[2 g], p4part[2 g + 1] over points kMkThreads g .. kMkThreads (g + 1) - 1 with the
+// association of a kMkThreads-thread workgroup (lane <-> point, DPP wave sums over 64 consecutive
+// points, the kMkWaves wave sums added in order from 0).  A wave takes U groups at a time and
+// issues their loads (16 bytes per point) before the first sum: one round trip to L2 for U groups,
+// not one per group.
+template <int NT>
+__device__ __forceinline__ void ba2_p4_partials(const BADesc& d, const BAWork2& w) {
+  constexpr int NW = NT / 64, U = 4;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const double2* pres2 = reinterpret_cast<const double2*>(w.pres);
+  for (int g0 = wave * U; g0 < w.gP; g0 += NW * U) {
+    double2 v[U][kMkWaves];
+#pragma unroll
+    for (int u = 0; u < U; u++)
+#pragma unroll
+      for (int q = 0; q < kMkWaves; q++) {
+        const int j = (g0 + u) * kMkThreads + 64 * q + lane;
+        v[u][q] = pres2[min(j, d.n_pt - 1)];
+      }
+#pragma unroll
+    for (int u = 0; u < U; u++) {
+      double t0 = 0, t1 = 0;
+#pragma unroll
+      for (int q = 0; q < kMkWaves; q++) {
+        const bool in = (g0 + u) * kMkThreads + 64 * q + lane < d.n_pt;
+        t0 += wave_sum_dpp(in ? v[u][q].x : 0.0);
+        t1 += wave_sum_dpp(in ? v[u][q].y : 0.0);
+      }
+      if (lane == 0 && g0 + u < w.gP) {
+        w.p4part[2 * (g0 + u)] = t0;
+        w.p4part[2 * (g0 + u) + 1] = t1;
+      }
+    }
   }
 }
 
-__global__ __launch_bounds__(kMkThreads) void k_ba2_p4(BADesc d, BAWork2 w) {
-  __shared__ double s_part[2 * kMkWaves];
+// trial step 4: the first gPp workgroups try the light points, a thread each, the others the heavy
+// points, a wave each; every point leaves its (trial chi2, scale) in pres.  The last workgroup to
+// finish, heavy ones included, takes the trial's decision (k_ba2_p5's work, one launch fewer per
+// trial): it rebuilds the partial sums from pres and runs ba2_decide.  The hand-off is a counter:
+// every wave drains its stores, the workgroup's barrier, one agent-scope release and the ticket by
+// thread 0; the last arriver's one agent-scope acquire (its wait held before the barrier) ahead of
+// the workgroup's loads of pres, err and the trial points.
+__global__ __launch_bounds__(kPtThreads) void k_ba2_p4(BADesc d, BAWork2 w) {
+  __shared__ double s_stage[kPtWaves][64];
   __shared__ int s_last;
   const BAState* st = w.st;
   if (st->done) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int j = blockIdx.x * kMkThreads + threadIdx.x;
-  double chi = 0, sc = 0;
-  if (j < d.n_pt) {
-    if (ba2_heavy(d, j)) {  // tried by its wave in k_ba2_p4_heavy
-      chi = w.hres[2 * (size_t)j];
-      sc = w.hres[2 * (size_t)j + 1];
-    } else {
+  const bool heavy_wg = (int)blockIdx.x >= w.gPp;
+  int j = blockIdx.x * kPtThreads + threadIdx.x;
+  bool mine = j < d.n_pt && !ba2_heavy(d, j);
+  if (heavy_wg) {
+    const int hi = ((int)blockIdx.x - w.gPp) * kPtWaves + wave;
+    mine = hi < w.n_heavy;
+    if (mine) j = w.heavy[hi];
+  }
+  if (mine) {
+    double chi, sc;
+    if (heavy_wg)
+      ba2_trial_point<true>(d, w, j, s_stage[wave], &chi, &sc);
+    else
       ba2_trial_point<false>(d, w, j, nullptr, &chi, &sc);
+    if (!heavy_wg || lane == 0) {
+      w.pres[2 * (size_t)j] = chi;
+      w.pres[2 * (size_t)j + 1] = sc;
     }
   }
-  const double a = wave_sum_dpp(chi), b = wave_sum_dpp(sc);
-  if (lane == 0) {
-    s_part[2 * wave] = a;
-    s_part[2 * wave + 1] = b;
-  }
-  __threadfence();  // release this thread's err / Xt stores to the deciding workgroup
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's pres / err / Xt stores
   __syncthreads();
   if (threadIdx.x == 0) {
-    double t0 = 0, t1 = 0;
-#pragma unroll
-    for (int q = 0; q < kMkWaves; q++) {
-      t0 += s_part[2 * q];
-      t1 += s_part[2 * q + 1];
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const unsigned done =
+        __hip_atomic_fetch_add(w.p4cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = done == (unsigned)gridDim.x - 1;
+    if (last) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    w.p4part[2 * blockIdx.x] = t0;
-    w.p4part[2 * blockIdx.x + 1] = t1;
-    // the last workgroup to finish takes the trial's decision (k_ba2_p5's work, one launch fewer
-    // per trial): its partials published by an agent-scope release (every thread's err / Xt
-    // stores were released by their own fence before the barrier above), the count, and the
-    // last one's acquire before it reads every partial
-    __threadfence();
-    const unsigned done = atomicAdd(w.p4cnt, 1u);
-    s_last = done == (unsigned)gridDim.x - 1;
-    if (s_last) __threadfence();
+    s_last = last;
   }
   __syncthreads();
   if (!s_last) return;
-  ba2_decide<kMkThreads>(d, w);
+  ba2_p4_partials<kPtThreads>(d, w);
+  __syncthreads();  // p4part (this workgroup's stores) before wave 0 adds it up
+  ba2_decide<kPtThreads>(d, w);
   if (threadIdx.x == 0) *w.p4cnt = 0;
 }
 
@@ -1630,9 +1674,9 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
   d.erase = d_dn_ + o_er;
   d.stats = (int*)(d_dn_ + o_st);
   {
-    const int gPp = std::max(1, (nP + kMkThreads - 1) / kMkThreads);
-    const int gH = ((int)heavy.size() + kMkWaves - 1) / kMkWaves;
-    const int gP = gPp;  // the partial sums: one per point workgroup
+    const int gPp = std::max(1, (nP + kPtThreads - 1) / kPtThreads);
+    const int gH = ((int)heavy.size() + kPtWaves - 1) / kPtWaves;
+    const int gP = std::max(1, (nP + kMkThreads - 1) / kMkThreads);  // the partial sums
     const int n6 = 6 * nO, nblk = nblocks;
     const size_t wsb2 = ba2_workspace_bytes(nK, nP, nE, nO, nblk, gP) +
                         8 * (27 + 6) * kitem.size() + 8 * 36 * bitem.size() + 16 * (size_t)nP +
@@ -1689,7 +1733,7 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
     w.gPp = gPp;
     w.heavy = (const int*)(u + off[18]);
     w.n_heavy = (int)heavy.size();
-    w.hres = (double*)take(16 * (size_t)nP);
+    w.pres = (double*)take(16 * (size_t)nP);
     w.spec = 0;  // k_ba2_lin linearises every trial (the trial kernel's own linearisation,
                  // k_ba2_p4<true>, measured 1,509 against 1,549 us per BA but spills)
     const double tp1 = hp.on ? ba_now_us() : 0;
@@ -1705,16 +1749,14 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
       const int batch = slots == 0 ? 15 : 4;
       const double tl = hp.on ? ba_now_us() : 0;
       for (int b = 0; b < batch; b++) {
-        if (gH > 0) hipLaunchKernelGGL(k_ba2_lin_heavy, dim3(gH), dim3(kMkThreads), 0, st, d, w);
-        hipLaunchKernelGGL(k_ba2_lin, dim3(gPp), dim3(kMkThreads), 0, st, d, w);
-        if (w.n_kitem > 0)
-          hipLaunchKernelGGL(k_ba2_kfsum, dim3(w.n_kitem), dim3(kMkThreads), 0, st, d, w);
-        hipLaunchKernelGGL(k_ba2_p1, dim3(gPp + gH), dim3(kMkThreads), 0, st, d, w);
+        hipLaunchKernelGGL(k_ba2_lin, dim3(gPp + gH), dim3(kPtThreads), 0, st, d, w);
+        // (with no keyframe item too: its last gP workgroups build linpart)
+        hipLaunchKernelGGL(k_ba2_kfsum, dim3(w.n_kitem + gP), dim3(kMkThreads), 0, st, d, w);
+        hipLaunchKernelGGL(k_ba2_p1, dim3(gPp + gH), dim3(kPtThreads), 0, st, d, w);
         if (w.n_bitem + w.n_kitem > 0)
           hipLaunchKernelGGL(k_ba2_p2, dim3(w.n_bitem + w.n_kitem), dim3(kMkThreads), 0, st, d, w);
         hipLaunchKernelGGL(k_ba2_p3, dim3(1), dim3(kMkSolveThreads), 0, st, d, w);
-        if (gH > 0) hipLaunchKernelGGL(k_ba2_p4_heavy, dim3(gH), dim3(kMkThreads), 0, st, d, w);
-        hipLaunchKernelGGL(k_ba2_p4, dim3(gPp), dim3(kMkThreads), 0, st, d, w);
+        hipLaunchKernelGGL(k_ba2_p4, dim3(gPp + gH), dim3(kPtThreads), 0, st, d, w);
       }
       MMT_HIP(hipGetLastError());
       slots += batch;

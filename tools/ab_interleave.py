@@ -1,8 +1,11 @@
 """Interleaved A/B of environment settings on one rendered sequence: the bench's C3 (and C2)
 workload tracked ROUNDS times per setting, settings alternating, each run in a fresh context
 (every knob the library reads at context creation or per call takes effect), frames/s per run and
-the median per setting.  Removes the box-to-box noise of separate bench runs.
-Usage: python tools/ab_interleave.py [--rounds 3] [--steps 6] [--chunk 128] [--c2] 'default' 'VAR=v,VAR2=w' ..."""
+the median per setting.  Removes the box-to-box noise of separate bench runs.  A setting that
+names MMT_LIB_PATH alternates library builds (tools/ab_build.sh) in the one process: the library is
+loaded again for that run.  --bench-form tracks as bench.py does (vocabulary loaded, deferred
+object results flushed inside the timed region).
+Usage: python tools/ab_interleave.py [--rounds 3] [--steps 6] [--chunk 128] [--bench-form] 'default' 'VAR=v,VAR2=w' ..."""
 import argparse
 import os
 import statistics
@@ -23,6 +26,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--chunk", type=int, default=128)
     ap.add_argument("--objects", type=int, default=3)
+    ap.add_argument("--bench-form", action="store_true")
+    ap.add_argument("--vocabulary", default=os.path.join(ROOT, "tests", "golden",
+                                                         "test_voc_k10l6.txt"))
     a = ap.parse_args()
     import torch
     import multimot_track_amd as M
@@ -40,6 +46,7 @@ def main():
     torch.cuda.set_stream(stream)
     base_env = dict(os.environ)
     res = {s: [] for s in a.settings}
+    loaded = None
     for r in range(a.rounds):
         for s in a.settings:
             os.environ.clear()
@@ -48,7 +55,14 @@ def main():
                 for kv in s.split(","):
                     k, v = kv.split("=", 1)
                     os.environ[k] = v
+            want = os.environ.get("MMT_LIB_PATH", M.LIB_PATH)
+            if M._LIB is not None and want != loaded:
+                M._LIB = None  # M.lib() loads the build this setting names
+            loaded = want
             ctx = M.Context(M.kitti03_config(W, H, NF, max_batch=C, device_id=0))
+            if a.bench_form:
+                ctx.load_vocabulary(a.vocabulary)
+                ctx.set_deferred_objects(True)
 
             def step(i):
                 sl = slice(i * C, (i + 1) * C)
@@ -60,6 +74,8 @@ def main():
             t0 = time.perf_counter()
             for i in range(a.steps):
                 step(a.warmup + i)
+            if a.bench_form:
+                ctx.flush_objects()
             torch.cuda.synchronize(dev)
             fps = a.steps * C / (time.perf_counter() - t0)
             ctx.close()
@@ -68,8 +84,9 @@ def main():
     os.environ.clear()
     os.environ.update(base_env)
     for s in a.settings:
-        print("%-40s median %8.1f  runs %s" % (s, statistics.median(res[s]),
-                                               " ".join("%.1f" % v for v in res[s])))
+        print("%-40s median %8.1f  spread %6.1f  runs %s" %
+              (s, statistics.median(res[s]), max(res[s]) - min(res[s]),
+               " ".join("%.1f" % v for v in res[s])))
 
 
 if __name__ == "__main__":
