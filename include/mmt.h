@@ -34,6 +34,12 @@
  *   mmt_search_by_bow   <- ORBmatcher::SearchByBoW(KeyFrame*, Frame&, vector<MapPoint*>&, ...)
  *                          ORBmatcher.cc:532-663 (TrackReferenceKeyFrame Tracking.cc:2841-2853,
  *                          Relocalization :3631-3651)
+ *   mmt_search_by_projection_keyframe
+ *                       <- ORBmatcher::SearchByProjection(Frame&, KeyFrame*, const set<MapPoint*>&,
+ *                          th, ORBdist) ORBmatcher.cc:2104-2231 (Relocalization :3717-3745)
+ *   mmt_search_for_triangulation
+ *                       <- LocalMapping::ComputeF12 + ORBmatcher::SearchForTriangulation
+ *                          ORBmatcher.cc:1032-1131 (CreateNewMapPoints LocalMapping.cc:253-264)
  *   mmt_fuse_candidates <- ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th)'s search,
  *                          ORBmatcher.cc:1200-1324 (LocalMapping::SearchInNeighbors
  *                          LocalMapping.cc:458-538)
@@ -467,6 +473,54 @@ int mmt_load_vocabulary(mmt_ctx* ctx, const char* path);
  * n x 32) on the GPU: word id, word weight (0: stopped) and the node at level L - levelsup. */
 int mmt_bow_transform(mmt_ctx* ctx, const uint8_t* desc, int n, int levelsup, uint32_t* word,
                       double* weight, uint32_t* node);
+
+/* The keyframe's map points as Relocalization's SearchByProjection reads them, in the keyframe's
+ * mvpMapPoints order: world position, mfMinDistance / mfMaxDistance, mDescriptor and the angle of
+ * the keyframe key that holds the point (pKF->mvKeysUn[i].angle). */
+typedef struct mmt_keyframe_points {
+  int m;
+  const float* Xw;        /* m x 3  */
+  const float* min_dist;  /* m      */
+  const float* max_dist;  /* m      */
+  const uint8_t* desc;    /* m x 32 */
+  const float* angle;     /* m      */
+} mmt_keyframe_points;
+
+/* Probe of ORBmatcher(0.9, true)::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)
+ * (ORBmatcher.cc:2104-2231) as Relocalization runs it: the code of the tracking path on
+ * caller-supplied arrays.  cur: the current frame and its pose; skip (m bytes) marks points that
+ * are bad or in sAlreadyFound; bound_in (cur->n bytes) marks current keys that hold a MapPoint when
+ * the call starts.  match_out[i] (cur->n) = the point (index into points) newly bound to key i, or
+ * -1, after the rotation histogram; *nmatches = the return value; *n_rescan (optional) = points
+ * whose 32 listed candidates were all bound by earlier points, so that the host rescanned their
+ * window. */
+int mmt_search_by_projection_keyframe(mmt_ctx* ctx, const mmt_match_frame* cur,
+                                      const mmt_keyframe_points* points, const uint8_t* skip,
+                                      float th, int orb_dist, const uint8_t* bound_in,
+                                      int32_t* match_out, int* nmatches, int* n_rescan);
+
+/* A keyframe as SearchForTriangulation reads it: mvKeysUn, mDescriptors, mvuRight (< 0: monocular),
+ * mFeatVec, whether mvpMapPoints[i] holds a MapPoint, and Tcw (row-major). */
+typedef struct mmt_sft_keyframe {
+  int n;
+  const mmt_kp* kps;
+  const uint8_t* desc;     /* n x 32 */
+  const float* uR;         /* n      */
+  const uint8_t* has_mp;   /* n      */
+  mmt_feature_vector fv;
+  float Tcw[16];
+} mmt_sft_keyframe;
+
+/* Probe of LocalMapping::CreateNewMapPoints' matching step (LocalMapping.cc:253-264): for each of
+ * the n_pairs neighbours kf2[p], ComputeF12(kf1, kf2[p]) and ORBmatcher(0.6, false)::
+ * SearchForTriangulation (ORBmatcher.cc:1032-1131), all pairs in one launch as on the tracking
+ * path.  match12_out[p * kf1->n + i] = the key of kf2[p] matched to key i of kf1, or -1; every pair
+ * runs against the same kf1 flags (the raw per-pair results, before CreateNewMapPoints drops the
+ * features an earlier neighbour triangulated).  F12_out (n_pairs x 9, row-major), nmatches
+ * (n_pairs).  Camera and scale pyramid from the context's configuration. */
+int mmt_search_for_triangulation(mmt_ctx* ctx, const mmt_sft_keyframe* kf1, int n_pairs,
+                                 const mmt_sft_keyframe* kf2, int32_t* match12_out,
+                                 float* F12_out, int* nmatches);
 
 /* Counters of the vocabulary path (tests): BoW conversions of frames, TrackReferenceKeyFrame calls
  * and successes, Relocalization calls and successes, candidate keyframes, PnPsolver poses,

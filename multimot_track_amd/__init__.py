@@ -188,6 +188,33 @@ class MmtBowKeyFrame(ctypes.Structure):
                 ("mp_valid", ctypes.c_void_p), ("fv", MmtFeatureVector)]
 
 
+class MmtKeyFramePoints(ctypes.Structure):
+    _fields_ = [("m", ctypes.c_int), ("Xw", ctypes.c_void_p), ("min_dist", ctypes.c_void_p),
+                ("max_dist", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("angle", ctypes.c_void_p)]
+
+
+class MmtSftKeyFrame(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("uR", ctypes.c_void_p), ("has_mp", ctypes.c_void_p), ("fv", MmtFeatureVector),
+                ("Tcw", ctypes.c_float * 16)]
+
+
+def _sft_keyframe(kf, keep):
+    """dict(kps, desc, uR, has_mp, fv, Tcw) -> MmtSftKeyFrame."""
+    k = np.ascontiguousarray(kf["kps"])
+    d = np.ascontiguousarray(kf["desc"], np.uint8)
+    u = np.ascontiguousarray(kf["uR"], np.float32)
+    h = np.ascontiguousarray(kf["has_mp"], np.uint8)
+    keep += [k, d, u, h]
+    s = MmtSftKeyFrame()
+    s.n = len(k)
+    s.kps, s.desc, s.uR, s.has_mp = k.ctypes.data, d.ctypes.data, u.ctypes.data, h.ctypes.data
+    s.fv = _feature_vector(kf["fv"], keep)
+    s.Tcw[:] = np.asarray(kf["Tcw"], np.float32).reshape(16).tolist()
+    return s
+
+
 def _feature_vector(v, keep):
     """(node ids ascending, starts (n_nodes + 1), features) -> MmtFeatureVector."""
     node, start, feat = (np.ascontiguousarray(v[0], np.uint32), np.ascontiguousarray(v[1], np.int32),
@@ -252,6 +279,10 @@ def lib():
         L.mmt_search_by_bow.argtypes = [vp, ctypes.POINTER(MmtBowKeyFrame), i32, vp, vp,
                                         ctypes.POINTER(MmtFeatureVector), ctypes.c_float, i32,
                                         vp, vp]
+        L.mmt_search_by_projection_keyframe.argtypes = [vp, ctypes.POINTER(MmtMatchFrame),
+                                                        ctypes.POINTER(MmtKeyFramePoints), vp,
+                                                        ctypes.c_float, i32, vp, vp, vp, vp]
+        L.mmt_search_for_triangulation.argtypes = [vp, vp, i32, vp, vp, vp, vp]
         L.mmt_profile_enable.argtypes = [vp, i32]
         L.mmt_profile_read.argtypes = [vp, ctypes.POINTER(MmtProfile), i32]
         L.mmt_fuse_candidates.argtypes = [vp, ctypes.POINTER(MmtMatchFrame),
@@ -540,6 +571,49 @@ class Context:
             self._h, ctypes.byref(fr), ctypes.byref(P), th,
             tk.ctypes.data if tk is not None else None, _p(match), _p(frus), ctypes.byref(nm)))
         return nm.value, match[:fr.n], frus[:P.m]
+
+    def search_by_projection_keyframe(self, kps, desc, depth, tcw, Xw, min_dist, max_dist, pdesc,
+                                      angle, skip, th, orb_dist, bound):
+        """Relocalization's ORBmatcher::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th,
+        ORBdist): (nmatches, match[cur key] = point index or -1, points that went through the
+        host rescan).  skip marks bad / already found points, bound the keys that hold a MapPoint
+        when the call starts."""
+        keep = []
+        fr = self._match_frame(kps, desc, depth, tcw, keep)
+        arrs = [np.ascontiguousarray(a, np.float32) for a in (Xw, min_dist, max_dist, angle)]
+        pd = np.ascontiguousarray(pdesc, np.uint8)
+        sk = np.ascontiguousarray(skip, np.uint8)
+        bd = np.ascontiguousarray(bound, np.uint8)
+        if len(bd) != fr.n or len(arrs[3]) != len(sk):
+            raise ValueError("bound / skip length")
+        P = MmtKeyFramePoints()
+        P.m = len(sk)
+        P.Xw, P.min_dist, P.max_dist, P.angle = [a.ctypes.data for a in arrs]
+        P.desc = pd.ctypes.data
+        match = np.zeros(max(fr.n, 1), np.int32)
+        nm, nr = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(lib().mmt_search_by_projection_keyframe(
+            self._h, ctypes.byref(fr), ctypes.byref(P), sk.ctypes.data, th, int(orb_dist),
+            bd.ctypes.data, _p(match), ctypes.byref(nm), ctypes.byref(nr)))
+        return nm.value, match[:fr.n], nr.value
+
+    def search_for_triangulation(self, kf1, kf2s):
+        """ComputeF12 + ORBmatcher::SearchForTriangulation of kf1 against every keyframe of kf2s
+        in one launch.  A keyframe is a dict(kps, desc, uR, has_mp, fv=(node ids, starts,
+        features), Tcw).  Returns (nmatches (n_pairs), match12 (n_pairs x n1: idx2 or -1), F12
+        (n_pairs x 3 x 3))."""
+        keep = []
+        a = _sft_keyframe(kf1, keep)
+        npairs = len(kf2s)
+        B = (MmtSftKeyFrame * max(npairs, 1))()
+        for p, kf in enumerate(kf2s):
+            B[p] = _sft_keyframe(kf, keep)
+        m12 = np.full(max(npairs, 1) * max(a.n, 1), -1, np.int32)
+        F = np.zeros((max(npairs, 1), 3, 3), np.float32)
+        nm = np.zeros(max(npairs, 1), np.int32)
+        self._check(lib().mmt_search_for_triangulation(
+            self._h, ctypes.addressof(a), npairs, ctypes.addressof(B), _p(m12), _p(F), _p(nm)))
+        return nm[:npairs], m12[:npairs * a.n].reshape(npairs, a.n), F[:npairs]
 
     def fuse_candidates(self, kps, desc, depth, tcw, Xw, normal, min_dist, max_dist, pdesc,
                         th=3.0):

@@ -126,4 +126,46 @@ struct SbpKfArgs {
 };
 void launch_sbp_kf(const SbpKfArgs& a, hipStream_t st);
 
+// ---- the two vocabulary-path matchers over flat arrays (mmt_bowmap.hip): what MapEngine runs on
+// the tracking path and what the C-ABI probes call.  Both stage their uploads and downloads through
+// one device block and one host block of equal size that the caller owns and grows.
+struct StageBuf {
+  uint8_t* d;
+  uint8_t* h;
+};
+struct Stage {
+  virtual ~Stage() {}
+  virtual StageBuf grow(size_t need) = 0;  // both blocks hold at least `need` bytes afterwards
+};
+
+struct MapCamH;
+void camera_centre(const float* Tcw, float* Ow);  // KeyFrame::GetCameraCenter: -Rcw^T tcw
+
+// SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) over the m listed points (the
+// keyframe's map points that are neither bad nor found, in keyframe order; angle[j] = the keyframe
+// key's): G the current frame on the device, kps / desc its host copies, bound[k] (G.n) = key k
+// holds a MapPoint when the call starts.  match[k] (G.n) = the listed point bound to key k by this
+// call, or -1; n_rescan (optional) = points that went through the host rescan.  Returns nmatches.
+int sbp_kf_flat(const GridFrame& G, const mmt_kp* kps, const uint8_t* desc, const float* Tcw,
+                const SbpKfPoint* pts, const float* angle, int m, const uint8_t* bound, float th,
+                int orbDist, int* match, int* n_rescan, Stage& stage, hipStream_t st);
+
+// A keyframe as SearchForTriangulation reads it: keys, descriptors and mvuRight on the device,
+// FeatureVector and has-MapPoint flags on the host, pose and camera centre.
+struct SftKeyFrame {
+  int n;
+  const mmt_kp* d_keys;
+  const uint8_t* d_desc;
+  const float* d_uR;
+  BowFeatVec fv;          // host arrays
+  const uint8_t* has_mp;  // n, host
+  const float* Tcw;
+  const float* Ow;
+};
+// SearchForTriangulation of keyframe 1 against np neighbours in one k_sft launch, F12 and the
+// epipole by ComputeF12 inside: match12[p * K1.n + idx1] = idx2 or -1 (every pair against the same
+// keyframe-1 flags), F12 (np x 9), nmatches (np).  Returns the number of queries.
+int sft_flat(const MapCamH& cam, const SftKeyFrame& K1, int np, const SftKeyFrame* K2,
+             int* match12, float* F12, int* nmatches, Stage& stage, hipStream_t st);
+
 }  // namespace mmt

@@ -97,6 +97,8 @@ void Vocabulary::load_text(const char* path) {
   for (size_t n = 1; n < parent.size(); n++)
     if (children[n].empty() != (leaf[n] != 0))
       throw ArgError("vocabulary node " + std::to_string(n) + ": leaf flag and children disagree");
+  // a header-only file: k_bow_transform's descent would read the children of a root without any
+  if (children[0].empty() || words_ == 0) throw ArgError("vocabulary: the file holds no word");
   child_start_.assign(1, 0);
   child_.clear();
   for (const auto& c : children) {

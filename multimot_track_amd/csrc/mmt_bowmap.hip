@@ -19,6 +19,7 @@
 #include <climits>
 #include <cmath>
 #include <cstring>
+#include <functional>
 
 #include "mmt_internal.h"
 #include "mmt_map.h"
@@ -183,6 +184,8 @@ void compute_f12(const float* T1, const float* T2, const MapCamH& cam, float F[9
 size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 }  // namespace
 
+void camera_centre(const float* Tcw, float* Ow) { cam_centre(Tcw, Ow); }
+
 // ------------------------------------------------------------------ glibc rand()
 GlibcRandH::GlibcRandH() {
   r_.resize(34);
@@ -230,6 +233,7 @@ void MapEngine::bow_launch(const uint8_t* d_desc, int n, hipStream_t st) {
   uint32_t* dw = (uint32_t*)d_bw_;
   uint32_t* dn = dw + n;
   double* dx = (double*)(d_bw_ + 8 * (size_t)n);
+  if (voc_->empty()) return;  // transform() of an empty vocabulary: build() leaves the vectors empty
   launch_bow_transform(voc_->dev, d_desc, n, 4, dw, dx, dn, st);
   if (n > 0) MMT_HIP(hipMemcpyAsync(h_bw_, d_bw_, 16 * (size_t)n, hipMemcpyDeviceToHost, st));
 }
@@ -426,51 +430,40 @@ bool MapEngine::track_reference_kf(MapFrameH& C, const GridFrame& G, float* Tcw,
 // ORBmatcher(0.9, true)::SearchByProjection(F, pKF, sAlreadyFound, th, ORBdist): k_sbp_kf's
 // candidate lists, then the binding in the keyframe's map-point order (a key bound by an earlier
 // point is skipped), the ORBdist test and the rotation histogram
-int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const float* Tcw, int kf,
-                                       const std::set<int>& found, float th, int orbDist) {
-  const KFrame& K = kfs_[kf];
-  std::vector<int> slot, hnd;
-  for (size_t i = 0; i < K.mps.size(); i++) {
-    const int h = K.mps[i];
-    if (h < 0 || pts_[h].bad || found.count(h)) continue;
-    slot.push_back((int)i);
-    hnd.push_back(h);
-  }
-  const int m = (int)slot.size();
+int sbp_kf_flat(const GridFrame& G, const mmt_kp* kps, const uint8_t* desc, const float* Tcw,
+                const SbpKfPoint* pts, const float* angle, int m, const uint8_t* bound_in, float th,
+                int orbDist, int* match, int* n_rescan, Stage& stage, hipStream_t st) {
+  const int n = G.n;
   const size_t o_p = 0, o_b = al16(sizeof(SbpKfPoint) * (size_t)m),
-               o_up = o_b + al16((size_t)C.n), o_k = o_up,
+               o_up = o_b + al16((size_t)n), o_k = o_up,
                o_i = o_k + al16(4 * (size_t)m * kSbpKfCand),
                o_n = o_i + al16(4 * (size_t)m * kSbpKfCand),
                o_w = o_n + al16(4 * (size_t)m), tot = o_w + sizeof(PointWin) * (size_t)m + 16;
-  bw_grow(tot);
-  uint8_t* h = h_bw_;
-  SbpKfPoint* P = (SbpKfPoint*)(h + o_p);
-  for (int j = 0; j < m; j++) {
-    const MPoint& p = pts_[hnd[j]];
-    memcpy(P[j].Xw, p.pos, 12);
-    P[j].min_dist = p.minDist;
-    P[j].max_dist = p.maxDist;
-    P[j].pad[0] = P[j].pad[1] = P[j].pad[2] = 0;
-    memcpy(P[j].desc, p.desc, 32);
+  const StageBuf sb = stage.grow(tot);
+  uint8_t* h = sb.h;
+  if (m > 0) memcpy(h + o_p, pts, sizeof(SbpKfPoint) * (size_t)m);
+  uint8_t* bound = h + o_b;  // keys bound when the call starts, then those this call binds
+  for (int i = 0; i < n; i++) {
+    bound[i] = bound_in[i] != 0;
+    match[i] = -1;
   }
-  for (int i = 0; i < C.n; i++) h[o_b + i] = C.mps[i] >= 0;
-  int nmatches = 0;
+  int nmatches = 0, rescans = 0;
   if (m > 0) {
-    MMT_HIP(hipMemcpyAsync(d_bw_, h_bw_, o_up, hipMemcpyHostToDevice, s_));
+    MMT_HIP(hipMemcpyAsync(sb.d, sb.h, o_up, hipMemcpyHostToDevice, st));
     SbpKfArgs a;
     a.C = G;
     memcpy(a.Tcw, Tcw, 64);
     a.th = th;
-    a.pts = (const SbpKfPoint*)(d_bw_ + o_p);
+    a.pts = (const SbpKfPoint*)(sb.d + o_p);
     a.m = m;
-    a.bound = d_bw_ + o_b;
-    a.cand_key = (uint32_t*)(d_bw_ + o_k);
-    a.cand_idx = (int*)(d_bw_ + o_i);
-    a.n_cand = (int*)(d_bw_ + o_n);
-    a.win = (PointWin*)(d_bw_ + o_w);
-    launch_sbp_kf(a, s_);
-    MMT_HIP(hipMemcpyAsync(h + o_k, d_bw_ + o_k, tot - o_k, hipMemcpyDeviceToHost, s_));
-    MMT_HIP(hipStreamSynchronize(s_));
+    a.bound = sb.d + o_b;
+    a.cand_key = (uint32_t*)(sb.d + o_k);
+    a.cand_idx = (int*)(sb.d + o_i);
+    a.n_cand = (int*)(sb.d + o_n);
+    a.win = (PointWin*)(sb.d + o_w);
+    launch_sbp_kf(a, st);
+    MMT_HIP(hipMemcpyAsync(h + o_k, sb.d + o_k, tot - o_k, hipMemcpyDeviceToHost, st));
+    MMT_HIP(hipStreamSynchronize(st));
   }
   const uint32_t* ck = (const uint32_t*)(h + o_k);
   const int* ci = (const int*)(h + o_i);
@@ -484,7 +477,7 @@ int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const f
     const int nk = std::min(nc[j], kSbpKfCand);
     for (int c = 0; c < nk; c++) {
       const int k = ci[(size_t)j * kSbpKfCand + c];
-      if (C.mps[k] >= 0) continue;  // bound by an earlier point of this call
+      if (bound[k]) continue;  // bound by an earlier point of this call
       best = k;
       bestDist = (int)(ck[(size_t)j * kSbpKfCand + c] >> 20);
       break;
@@ -492,21 +485,22 @@ int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const f
     if (best < 0 && nc[j] > kSbpKfCand) {
       // every listed candidate was taken by earlier points: rescan the window on the host in
       // GetFeaturesInArea order (cells ix, iy ascending, keys ascending in a cell)
+      rescans++;
       const PointWin& w = win[j];
       const int cx0 = std::max(0, (int)std::floor((w.x - G.minX - w.r) * G.invW));
       const int cx1 = std::min(kGridCols - 1, (int)std::ceil((w.x - G.minX + w.r) * G.invW));
       const int cy0 = std::max(0, (int)std::floor((w.y - G.minY - w.r) * G.invH));
       const int cy1 = std::min(kGridRows - 1, (int)std::ceil((w.y - G.minY + w.r) * G.invH));
       long bestKey = LONG_MAX;
-      for (int k = 0; k < C.n; k++) {
-        const mmt_kp& kp = C.kps[k];
-        const int px = (int)std::round((kp.x - 0.0f) * G.invW);
-        const int py = (int)std::round((kp.y - 0.0f) * G.invH);
+      for (int k = 0; k < n; k++) {
+        const mmt_kp& kp = kps[k];
+        const int px = (int)std::round((kp.x - G.minX) * G.invW);  // Frame::PosInGrid
+        const int py = (int)std::round((kp.y - G.minY) * G.invH);
         if (px < cx0 || px > cx1 || py < cy0 || py > cy1) continue;
         if (kp.octave < w.minLevel || (w.maxLevel >= 0 && kp.octave > w.maxLevel)) continue;
         if (!(std::fabs(kp.x - w.x) < w.r && std::fabs(kp.y - w.y) < w.r)) continue;
-        if (C.mps[k] >= 0) continue;
-        const int dist = hamming(pts_[hnd[j]].desc, C.desc + 32 * (size_t)k);
+        if (bound[k]) continue;
+        const int dist = hamming(pts[j].desc, desc + 32 * (size_t)k);
         const long key = ((long)dist << 40) | ((long)(px * kGridRows + py) << 20) | k;
         if (key < bestKey) {
           bestKey = key;
@@ -516,9 +510,10 @@ int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const f
       }
     }
     if (best < 0 || bestDist > orbDist) continue;
-    C.mps[best] = hnd[j];
+    bound[best] = 1;
+    match[best] = j;
     nmatches++;
-    float rot = K.keys[slot[j]].angle - C.kps[best].angle;
+    float rot = angle[j] - kps[best].angle;
     if (rot < 0.0) rot += 360.0f;
     int bin = (int)std::round(rot * factor);
     if (bin == HISTO_LENGTH) bin = 0;
@@ -529,10 +524,54 @@ int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const f
   for (int i = 0; i < HISTO_LENGTH; i++) {
     if (i == ind1 || i == ind2 || i == ind3) continue;
     for (int j : rotHist[i]) {
-      C.mps[j] = -1;
+      match[j] = -1;
       nmatches--;
     }
   }
+  if (n_rescan) *n_rescan = rescans;
+  return nmatches;
+}
+
+namespace {
+struct EngineStage : Stage {  // MapEngine's d_bw_ / h_bw_
+  std::function<StageBuf(size_t)> f;
+  StageBuf grow(size_t need) override { return f(need); }
+};
+}  // namespace
+
+// the keyframe's map points that are neither bad nor found, gathered for sbp_kf_flat
+int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const float* Tcw, int kf,
+                                       const std::set<int>& found, float th, int orbDist) {
+  const KFrame& K = kfs_[kf];
+  std::vector<int> hnd;
+  std::vector<SbpKfPoint> P;
+  std::vector<float> angle;
+  for (size_t i = 0; i < K.mps.size(); i++) {
+    const int h = K.mps[i];
+    if (h < 0 || pts_[h].bad || found.count(h)) continue;
+    const MPoint& p = pts_[h];
+    SbpKfPoint q;
+    memcpy(q.Xw, p.pos, 12);
+    q.min_dist = p.minDist;
+    q.max_dist = p.maxDist;
+    q.pad[0] = q.pad[1] = q.pad[2] = 0;
+    memcpy(q.desc, p.desc, 32);
+    P.push_back(q);
+    angle.push_back(K.keys[i].angle);
+    hnd.push_back(h);
+  }
+  std::vector<uint8_t> bound(std::max(C.n, 1));
+  for (int i = 0; i < C.n; i++) bound[i] = C.mps[i] >= 0;
+  std::vector<int> match(std::max(C.n, 1), -1);
+  EngineStage stage;
+  stage.f = [this](size_t need) {
+    bw_grow(need);
+    return StageBuf{d_bw_, h_bw_};
+  };
+  const int nmatches = sbp_kf_flat(G, C.kps, C.desc, Tcw, P.data(), angle.data(), (int)P.size(),
+                                   bound.data(), th, orbDist, match.data(), nullptr, stage, s_);
+  for (int i = 0; i < C.n; i++)
+    if (match[i] >= 0) C.mps[i] = hnd[match[i]];
   return nmatches;
 }
 
@@ -670,10 +709,98 @@ bool MapEngine::relocalization(MapFrameH& C, const GridFrame& G, float* Tcw) {
   return bMatch;
 }
 
+// SearchForTriangulation of keyframe 1 against every listed neighbour in one k_sft launch: one
+// query per keyframe-1 feature without a MapPoint in a vocabulary node both keyframes hold
+int sft_flat(const MapCamH& cam, const SftKeyFrame& K1, int np, const SftKeyFrame* K2s,
+             int* match12, float* F12, int* nmatches, Stage& stage, hipStream_t st) {
+  for (size_t i = 0; i < (size_t)np * (size_t)K1.n; i++) match12[i] = -1;
+  for (int p = 0; p < np; p++) nmatches[p] = 0;
+  if (np <= 0) return 0;
+  std::vector<SftQuery> q;
+  std::vector<size_t> o_feat(np), o_tak(np);
+  size_t off = al16(sizeof(SftPair) * (size_t)np);
+  for (int p = 0; p < np; p++) {
+    const SftKeyFrame& K2 = K2s[p];
+    const BowFeatVec& f1 = K1.fv;
+    const BowFeatVec& f2 = K2.fv;
+    const size_t nfeat2 = f2.n_nodes > 0 ? (size_t)f2.start[f2.n_nodes] : 0;
+    o_feat[p] = off;
+    off += al16(4 * nfeat2 + 4);
+    o_tak[p] = off;
+    off += al16((size_t)K2.n + 1);
+    int a = 0, b = 0;
+    while (a < f1.n_nodes && b < f2.n_nodes) {
+      if (f1.node[a] == f2.node[b]) {
+        for (int i = f1.start[a]; i < f1.start[a + 1]; i++) {
+          const int idx1 = f1.feat[i];
+          if (K1.has_mp[idx1]) continue;
+          q.push_back(SftQuery{p, idx1, f2.start[b], f2.start[b + 1]});
+        }
+        a++;
+        b++;
+      } else if (f1.node[a] < f2.node[b]) {
+        a = (int)(std::lower_bound(f1.node, f1.node + f1.n_nodes, f2.node[b]) - f1.node);
+      } else {
+        b = (int)(std::lower_bound(f2.node, f2.node + f2.n_nodes, f1.node[a]) - f2.node);
+      }
+    }
+  }
+  const int nq = (int)q.size();
+  const size_t o_q = off, o_up = o_q + al16(sizeof(SftQuery) * (size_t)std::max(nq, 1)),
+               o_out = o_up, tot = o_out + 4 * (size_t)std::max(nq, 1);
+  const StageBuf sb = stage.grow(tot);
+  uint8_t* h = sb.h;
+  SftPair* P = (SftPair*)h;
+  for (int p = 0; p < np; p++) {
+    const SftKeyFrame& K2 = K2s[p];
+    const size_t nfeat2 = K2.fv.n_nodes > 0 ? (size_t)K2.fv.start[K2.fv.n_nodes] : 0;
+    P[p].k2 = K2.d_keys;
+    P[p].d2 = K2.d_desc;
+    P[p].uR2 = K2.d_uR;
+    P[p].feat2 = (const int*)(sb.d + o_feat[p]);
+    P[p].taken2 = sb.d + o_tak[p];
+    compute_f12(K1.Tcw, K2.Tcw, cam, P[p].F12);
+    memcpy(F12 + 9 * (size_t)p, P[p].F12, sizeof(P[p].F12));
+    float C2[3];  // the epipole of keyframe 1 in keyframe 2
+    xform(K2.Tcw, K1.Ow, C2);
+    const float invz = 1.0f / C2[2];
+    P[p].ex = cam.fx * C2[0] * invz + cam.cx;
+    P[p].ey = cam.fy * C2[1] * invz + cam.cy;
+    if (nfeat2 > 0) memcpy(h + o_feat[p], K2.fv.feat, 4 * nfeat2);
+    for (int i = 0; i < K2.n; i++) h[o_tak[p] + i] = K2.has_mp[i] != 0;
+  }
+  if (nq == 0) return 0;
+  memcpy(h + o_q, q.data(), sizeof(SftQuery) * (size_t)nq);
+  std::vector<int> best(nq, -1);
+  MMT_HIP(hipMemcpyAsync(sb.d, sb.h, o_up, hipMemcpyHostToDevice, st));
+  SftArgs a;
+  a.k1 = K1.d_keys;
+  a.d1 = K1.d_desc;
+  a.uR1 = K1.d_uR;
+  a.pairs = (const SftPair*)sb.d;
+  a.q = (const SftQuery*)(sb.d + o_q);
+  a.nq = nq;
+  for (int l = 0; l < kMaxLevels; l++) a.scale[l] = a.sigma2[l] = 0.f;
+  for (int l = 0; l < cam.nlevels && l < kMaxLevels; l++) {
+    a.scale[l] = cam.scale[l];
+    a.sigma2[l] = cam.scale[l] * cam.scale[l];
+  }
+  a.out = (int*)(sb.d + o_out);
+  launch_sft(a, st);
+  MMT_HIP(hipMemcpyAsync(best.data(), sb.d + o_out, 4 * (size_t)nq, hipMemcpyDeviceToHost, st));
+  MMT_HIP(hipStreamSynchronize(st));
+  for (int i = 0; i < nq; i++)
+    if (best[i] >= 0) {
+      match12[(size_t)q[i].pair * (size_t)K1.n + q[i].idx1] = best[i];
+      nmatches[q[i].pair]++;
+    }
+  return nq;
+}
+
 // LocalMapping::CreateNewMapPoints (LocalMapping.cc:210-456), RGB-D branch: SearchForTriangulation
-// of every neighbour in one k_sft launch (the queries of neighbour i whose keyframe-1 feature got
-// a point from an earlier neighbour are dropped, as the reference skips them; neighbour i's own
-// keyframe is touched by no earlier neighbour), then the triangulation on the host
+// of every neighbour in one k_sft launch (sft_flat; the matches of neighbour i whose keyframe-1
+// feature got a point from an earlier neighbour are dropped, as the reference skips them;
+// neighbour i's own keyframe is touched by no earlier neighbour), then the triangulation on the host
 void MapEngine::create_new_map_points(int kf) {
   std::vector<int> neigh;
   {
@@ -682,105 +809,51 @@ void MapEngine::create_new_map_points(int kf) {
   }
   const float ratioFactor = 1.5f * cam_.scale[1];
   const float mb = cam_.bf / cam_.fx;
-  struct PairH {
-    int k2;
-    float F12[9];
-    float ex, ey;
-  };
-  std::vector<PairH> pairs;
+  std::vector<int> pairs;
   for (int k2 : neigh) {
     const KFrame& K1 = kfs_[kf];
     const KFrame& K2 = kfs_[k2];
     const float vB[3] = {K2.Ow[0] - K1.Ow[0], K2.Ow[1] - K1.Ow[1], K2.Ow[2] - K1.Ow[2]};
     if (norm3(vB) < mb) continue;
-    PairH p;
-    p.k2 = k2;
-    compute_f12(K1.Tcw, K2.Tcw, cam_, p.F12);
-    float C2[3];
-    xform(K2.Tcw, K1.Ow, C2);
-    const float invz = 1.0f / C2[2];
-    p.ex = cam_.fx * C2[0] * invz + cam_.cx;
-    p.ey = cam_.fy * C2[1] * invz + cam_.cy;
-    pairs.push_back(p);
+    pairs.push_back(k2);
   }
   if (pairs.empty()) return;
-  const KFrame& K1 = kfs_[kf];
-  const int np = (int)pairs.size();
-  std::vector<SftQuery> q;
-  std::vector<size_t> o_feat(np), o_tak(np);
-  size_t off = al16(sizeof(SftPair) * (size_t)np);
+  const int np = (int)pairs.size(), n1 = (int)kfs_[kf].keys.size();
+  std::vector<std::vector<uint8_t>> has(np + 1);
+  auto view = [&](int k, std::vector<uint8_t>& flags) {
+    const KFrame& K = kfs_[k];
+    flags.resize(K.keys.size() + 1);
+    for (size_t i = 0; i < K.keys.size(); i++) flags[i] = K.mps[i] >= 0;
+    SftKeyFrame v;
+    v.n = (int)K.keys.size();
+    v.d_keys = K.dev.keys;
+    v.d_desc = K.dev.desc;
+    v.d_uR = K.dev.uR;
+    v.fv = BowFeatVec{(int)K.fv.node.size(), K.fv.node.data(), K.fv.start.data(), K.fv.feat.data()};
+    v.has_mp = flags.data();
+    v.Tcw = K.Tcw;
+    v.Ow = K.Ow;
+    return v;
+  };
+  const SftKeyFrame V1 = view(kf, has[np]);
+  std::vector<SftKeyFrame> V2(np);
+  for (int p = 0; p < np; p++) V2[p] = view(pairs[p], has[p]);
+  std::vector<int> match12((size_t)np * (size_t)std::max(n1, 1), -1), nm(np, 0);
+  std::vector<float> F12(9 * (size_t)np);
+  EngineStage stage;
+  stage.f = [this](size_t need) {
+    bw_grow(need);
+    return StageBuf{d_bw_, h_bw_};
+  };
+  sft_flat(cam_, V1, np, V2.data(), match12.data(), F12.data(), nm.data(), stage, lm_s_);
   for (int p = 0; p < np; p++) {
-    const KFrame& K2 = kfs_[pairs[p].k2];
-    o_feat[p] = off;
-    off += al16(4 * K2.fv.feat.size() + 4);
-    o_tak[p] = off;
-    off += al16(K2.keys.size() + 1);
-    size_t a = 0, b = 0;
-    const FeatVecH& f1 = K1.fv;
-    const FeatVecH& f2 = K2.fv;
-    while (a < f1.node.size() && b < f2.node.size()) {
-      if (f1.node[a] == f2.node[b]) {
-        for (int i = f1.start[a]; i < f1.start[a + 1]; i++) {
-          const int idx1 = f1.feat[i];
-          if (K1.mps[idx1] >= 0) continue;
-          q.push_back(SftQuery{p, idx1, f2.start[b], f2.start[b + 1]});
-        }
-        a++;
-        b++;
-      } else if (f1.node[a] < f2.node[b]) {
-        a = (size_t)(std::lower_bound(f1.node.begin(), f1.node.end(), f2.node[b]) - f1.node.begin());
-      } else {
-        b = (size_t)(std::lower_bound(f2.node.begin(), f2.node.end(), f1.node[a]) - f2.node.begin());
-      }
-    }
-  }
-  const int nq = (int)q.size();
-  const size_t o_q = off, o_up = o_q + al16(sizeof(SftQuery) * (size_t)std::max(nq, 1)),
-               o_out = o_up, tot = o_out + 4 * (size_t)std::max(nq, 1);
-  bw_grow(tot);
-  uint8_t* h = h_bw_;
-  SftPair* P = (SftPair*)h;
-  for (int p = 0; p < np; p++) {
-    const KFrame& K2 = kfs_[pairs[p].k2];
-    P[p].k2 = K2.dev.keys;
-    P[p].d2 = K2.dev.desc;
-    P[p].uR2 = K2.dev.uR;
-    P[p].feat2 = (const int*)(d_bw_ + o_feat[p]);
-    P[p].taken2 = d_bw_ + o_tak[p];
-    memcpy(P[p].F12, pairs[p].F12, sizeof(P[p].F12));
-    P[p].ex = pairs[p].ex;
-    P[p].ey = pairs[p].ey;
-    memcpy(h + o_feat[p], K2.fv.feat.data(), 4 * K2.fv.feat.size());
-    for (size_t i = 0; i < K2.keys.size(); i++) h[o_tak[p] + i] = K2.mps[i] >= 0;
-  }
-  memcpy(h + o_q, q.data(), sizeof(SftQuery) * (size_t)nq);
-  std::vector<int> best(std::max(nq, 1), -1);
-  if (nq > 0) {
-    MMT_HIP(hipMemcpyAsync(d_bw_, h_bw_, o_up, hipMemcpyHostToDevice, lm_s_));
-    SftArgs a;
-    a.k1 = K1.dev.keys;
-    a.d1 = K1.dev.desc;
-    a.uR1 = K1.dev.uR;
-    a.pairs = (const SftPair*)d_bw_;
-    a.q = (const SftQuery*)(d_bw_ + o_q);
-    a.nq = nq;
-    for (int l = 0; l < cam_.nlevels && l < kMaxLevels; l++) {
-      a.scale[l] = cam_.scale[l];
-      a.sigma2[l] = cam_.scale[l] * cam_.scale[l];
-    }
-    a.out = (int*)(d_bw_ + o_out);
-    launch_sft(a, lm_s_);
-    MMT_HIP(hipMemcpyAsync(best.data(), d_bw_ + o_out, 4 * (size_t)nq, hipMemcpyDeviceToHost, lm_s_));
-    MMT_HIP(hipStreamSynchronize(lm_s_));
-  }
-  size_t qi = 0;
-  for (int p = 0; p < np; p++) {
-    const int k2 = pairs[p].k2;
+    const int k2 = pairs[p];
     // vMatchedPairs in keyframe-1 key order, over the features still without a MapPoint
     std::vector<std::pair<int, int>> mp12;
-    for (; qi < q.size() && q[qi].pair == p; qi++)
-      if (best[qi] >= 0 && kfs_[kf].mps[q[qi].idx1] < 0) mp12.push_back({q[qi].idx1, best[qi]});
-    std::sort(mp12.begin(), mp12.end());
+    for (int i = 0; i < n1; i++) {
+      const int idx2 = match12[(size_t)p * (size_t)n1 + i];
+      if (idx2 >= 0 && kfs_[kf].mps[i] < 0) mp12.push_back({i, idx2});
+    }
     bstats_.n_sft_matches += (long)mp12.size();
     const float* T1 = kfs_[kf].Tcw;
     const float* T2 = kfs_[k2].Tcw;

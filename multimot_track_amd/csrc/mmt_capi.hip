@@ -44,6 +44,22 @@ struct DevBuf {
   ~DevBuf() { (void)hipFree(p); }
 };
 
+// The staging blocks of a vocabulary-path matcher probe (MapEngine's own on the tracking path).
+struct ProbeStage : mmt::Stage {
+  uint8_t* d = nullptr;
+  std::vector<uint8_t> h;
+  ~ProbeStage() override { (void)hipFree(d); }
+  mmt::StageBuf grow(size_t need) override {
+    if (need > h.size() || !d) {
+      (void)hipFree(d);
+      d = nullptr;
+      MMT_HIP(hipMalloc((void**)&d, std::max<size_t>(need, 16)));
+      h.assign(std::max<size_t>(need, 16), 0);
+    }
+    return mmt::StageBuf{d, h.data()};
+  }
+};
+
 // The current frame of a matcher probe on the device: keys, descriptors, depth map, and the B3
 // outputs (uR, depth, grid) built by k_stereo_grid.
 struct DevMatchFrame {
@@ -896,6 +912,14 @@ int mmt_bow_transform(mmt_ctx* ctx, const uint8_t* desc, int n, int levelsup, ui
     if (!ctx->voc) throw mmt::ArgError("mmt_bow_transform: no vocabulary loaded");
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     if (n == 0) return;
+    if (ctx->voc->empty()) {  // TemplatedVocabulary.h:1134: nothing is transformed
+      for (int i = 0; i < n; i++) {
+        word[i] = 0;
+        weight[i] = 0.0;
+        node[i] = 0;
+      }
+      return;
+    }
     ctx->voc->upload();
     hipStream_t s = ctx->stream;
     DevBuf<uint8_t> d(32 * (size_t)n);
@@ -987,6 +1011,116 @@ int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const
       MMT_HIP(hipMemcpyAsync(match_out, match.p, 4 * (size_t)n_cur, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipMemcpyAsync(nmatches, cnt.p + 1, 4, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int mmt_search_by_projection_keyframe(mmt_ctx* ctx, const mmt_match_frame* cur,
+                                      const mmt_keyframe_points* pts, const uint8_t* skip,
+                                      float th, int orb_dist, const uint8_t* bound_in,
+                                      int32_t* match_out, int* nmatches, int* n_rescan) {
+  if (!ctx || !cur || !pts || !nmatches || pts->m < 0 ||
+      (cur->n > 0 && (!match_out || !bound_in)) ||
+      (pts->m > 0 && (!pts->Xw || !pts->min_dist || !pts->max_dist || !pts->desc ||
+                      !pts->angle || !skip)))
+    return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_match_frame(ctx, cur, true);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    DevMatchFrame F(ctx, cur, true);
+    std::vector<mmt::SbpKfPoint> P;
+    std::vector<float> angle;
+    std::vector<int> src;  // listed point -> index into pts
+    for (int j = 0; j < pts->m; j++) {
+      if (skip[j]) continue;
+      mmt::SbpKfPoint p;
+      memset(&p, 0, sizeof(p));
+      memcpy(p.Xw, pts->Xw + 3 * (size_t)j, 12);
+      p.min_dist = pts->min_dist[j];
+      p.max_dist = pts->max_dist[j];
+      memcpy(p.desc, pts->desc + 32 * (size_t)j, 32);
+      P.push_back(p);
+      angle.push_back(pts->angle[j]);
+      src.push_back(j);
+    }
+    ProbeStage stage;
+    std::vector<int> match(std::max(cur->n, 1), -1);
+    *nmatches = mmt::sbp_kf_flat(F.G, cur->kps, cur->desc, cur->Tcw, P.data(), angle.data(),
+                                 (int)P.size(), bound_in, th, orb_dist, match.data(), n_rescan,
+                                 stage, s);
+    for (int i = 0; i < cur->n; i++) match_out[i] = match[i] >= 0 ? src[match[i]] : -1;
+  });
+}
+
+static void check_sft_keyframe(const mmt_sft_keyframe* k) {
+  if (k->n < 0 || k->n > mmt::kMaxMatchKeys) throw ArgError("bad keyframe size");
+  if (k->n > 0 && (!k->kps || !k->desc || !k->uR || !k->has_mp))
+    throw ArgError("null keyframe arrays");
+  std::vector<uint8_t> once((size_t)std::max(k->n, 1), 0);
+  check_feature_vector(&k->fv, k->n, &once, INT32_MAX);
+}
+
+int mmt_search_for_triangulation(mmt_ctx* ctx, const mmt_sft_keyframe* kf1, int n_pairs,
+                                 const mmt_sft_keyframe* kf2, int32_t* match12_out,
+                                 float* F12_out, int* nmatches) {
+  if (!ctx || !kf1 || n_pairs < 0 ||
+      (n_pairs > 0 && (!kf2 || !F12_out || !nmatches || (kf1->n > 0 && !match12_out))))
+    return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (ctx->orb.nlevels > mmt::kMaxLevels) throw ArgError("too many pyramid levels");
+    check_sft_keyframe(kf1);
+    for (int p = 0; p < n_pairs; p++) check_sft_keyframe(kf2 + p);
+    auto octaves = [&](const mmt_sft_keyframe* k) {
+      for (int i = 0; i < k->n; i++)
+        if (k->kps[i].octave < 0 || k->kps[i].octave >= ctx->orb.nlevels)
+          throw ArgError("keypoint octave out of range");
+    };
+    octaves(kf1);
+    for (int p = 0; p < n_pairs; p++) octaves(kf2 + p);
+    if (n_pairs == 0) return;
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    mmt::MapCamH cam;
+    cam.fx = ctx->cfg.fx; cam.fy = ctx->cfg.fy; cam.cx = ctx->cfg.cx; cam.cy = ctx->cfg.cy;
+    cam.bf = ctx->cfg.bf;
+    cam.nlevels = ctx->orb.nlevels;
+    cam.scale.assign(ctx->orb.scale.begin(), ctx->orb.scale.end());
+    struct DevKF {
+      DevBuf<mmt_kp> kps;
+      DevBuf<uint8_t> desc;
+      DevBuf<float> uR;
+      float Ow[3];
+      explicit DevKF(int n) : kps(n), desc(32 * (size_t)n), uR(n) {}
+    };
+    std::vector<std::unique_ptr<DevKF>> dev;
+    auto view = [&](const mmt_sft_keyframe* k) {
+      dev.emplace_back(new DevKF(k->n));
+      DevKF& D = *dev.back();
+      if (k->n > 0) {
+        MMT_HIP(hipMemcpyAsync(D.kps.p, k->kps, sizeof(mmt_kp) * (size_t)k->n,
+                               hipMemcpyHostToDevice, s));
+        MMT_HIP(hipMemcpyAsync(D.desc.p, k->desc, 32 * (size_t)k->n, hipMemcpyHostToDevice, s));
+        MMT_HIP(hipMemcpyAsync(D.uR.p, k->uR, 4 * (size_t)k->n, hipMemcpyHostToDevice, s));
+      }
+      mmt::camera_centre(k->Tcw, D.Ow);
+      mmt::SftKeyFrame v;
+      v.n = k->n;
+      v.d_keys = D.kps.p;
+      v.d_desc = D.desc.p;
+      v.d_uR = D.uR.p;
+      v.fv = mmt::BowFeatVec{k->fv.n_nodes, k->fv.node_id, k->fv.node_start, k->fv.feat};
+      v.has_mp = k->has_mp;
+      v.Tcw = k->Tcw;
+      v.Ow = D.Ow;
+      return v;
+    };
+    const mmt::SftKeyFrame V1 = view(kf1);
+    std::vector<mmt::SftKeyFrame> V2;
+    for (int p = 0; p < n_pairs; p++) V2.push_back(view(kf2 + p));
+    ProbeStage stage;
+    std::vector<int> m12((size_t)n_pairs * (size_t)std::max(kf1->n, 1), -1);
+    mmt::sft_flat(cam, V1, n_pairs, V2.data(), m12.data(), F12_out, nmatches, stage, s);
+    if (kf1->n > 0) memcpy(match12_out, m12.data(), 4 * (size_t)n_pairs * (size_t)kf1->n);
   });
 }
 

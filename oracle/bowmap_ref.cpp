@@ -136,6 +136,8 @@ void null_vector4(const float A[16], float v_out[4]) {
   for (int k = 0; k < 4; k++) v_out[k] = (float)(V[k][m] / n);
 }
 
+}  // namespace
+
 // LocalMapping::ComputeF12 (pinned: double from the float poses, one float rounding)
 void compute_f12(const float* T1, const float* T2, const MapCam& cam, float F[9]) {
   double R12[3][3], t12[3];
@@ -175,6 +177,7 @@ void compute_f12(const float* T1, const float* T2, const MapCam& cam, float F[9]
     }
 }
 
+namespace {
 // ORBmatcher::CheckDistEpipolarLine
 bool check_epipolar(const Key& kp1, const Key& kp2, const float* F, const MapCam& cam) {
   const float a = kp1.x * F[0] + kp1.y * F[3] + F[6];
@@ -314,51 +317,52 @@ bool MapTracker::track_reference_kf(const std::vector<Key>& keys, const std::vec
 
 // ORBmatcher(0.9, true)::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)
 // (ORBmatcher.cc:2104-2231)
-int MapTracker::search_by_projection_kf(const std::vector<Key>& keys,
-                                        const std::vector<uint8_t>& desc, MapFrame& C,
-                                        const float* Tcw, int kf, const std::set<int>& found,
-                                        float th, int orbDist) {
-  MatchFrame G;
-  build_grid(keys, desc, C, G);
+int search_by_projection_kf_arrays(const MatchFrame& G, const float* Tcw, int m, const float* Xw,
+                                   const float* min_dist, const float* max_dist,
+                                   const uint8_t* pdesc, const float* angle, const uint8_t* skip,
+                                   float th, int orbDist, const uint8_t* bound_in, int* match) {
+  std::vector<uint8_t> bound(bound_in, bound_in + G.n);  // mvpMapPoints[i2] != NULL
+  for (int k = 0; k < G.n; k++) match[k] = -1;
   float Ow[3];
   cam_centre(Tcw, Ow);
   std::vector<int> rotHist[HISTO_LENGTH];
   const float factor = 1.0f / HISTO_LENGTH;
-  const OKeyFrame& K = kfs[kf];
+  MapCam cam;  // PredictScale reads the frame's pyramid
+  cam.logScale = G.logScale;
+  cam.nlevels = G.nlevels;
   int nmatches = 0;
-  for (size_t i = 0; i < K.mps.size(); i++) {
-    const int h = K.mps[i];
-    if (h < 0) continue;
-    const OMapPoint& p = mp(h);
-    if (p.bad || found.count(h)) continue;
+  for (int i = 0; i < m; i++) {
+    if (skip[i]) continue;
+    const float* pos = Xw + 3 * (size_t)i;
     float x3Dc[3];
-    xform(Tcw, p.pos, x3Dc);
+    xform(Tcw, pos, x3Dc);
     const float invzc = (float)(1.0 / x3Dc[2]);
-    const float u = cam.fx * x3Dc[0] * invzc + cam.cx;
-    const float v = cam.fy * x3Dc[1] * invzc + cam.cy;
+    const float u = G.fx * x3Dc[0] * invzc + G.cx;
+    const float v = G.fy * x3Dc[1] * invzc + G.cy;
     if (u < G.minX || u > G.maxX) continue;
     if (v < G.minY || v > G.maxY) continue;
-    const float PO[3] = {p.pos[0] - Ow[0], p.pos[1] - Ow[1], p.pos[2] - Ow[2]};
+    const float PO[3] = {pos[0] - Ow[0], pos[1] - Ow[1], pos[2] - Ow[2]};
     const float dist3D = norm3(PO);
-    const float maxDistance = 1.2f * p.maxDist, minDistance = 0.8f * p.minDist;
+    const float maxDistance = 1.2f * max_dist[i], minDistance = 0.8f * min_dist[i];
     if (dist3D < minDistance || dist3D > maxDistance) continue;
-    const int npl = predict_scale(p.maxDist, dist3D, cam);
-    const float radius = th * cam.scale[npl];
+    const int npl = predict_scale(max_dist[i], dist3D, cam);
+    const float radius = th * G.scale[npl];
     const std::vector<int> idx = features_in_area(G, u, v, radius, npl - 1, npl + 1);
     if (idx.empty()) continue;
     int bestDist = 256, bestIdx2 = -1;
     for (int i2 : idx) {
-      if (C.mps[i2] >= 0) continue;
-      const int dist = descriptor_distance(p.desc, desc.data() + 32 * (size_t)i2);
+      if (bound[i2]) continue;
+      const int dist = descriptor_distance(pdesc + 32 * (size_t)i, G.desc + 32 * (size_t)i2);
       if (dist < bestDist) {
         bestDist = dist;
         bestIdx2 = i2;
       }
     }
     if (bestDist <= orbDist) {
-      C.mps[bestIdx2] = h;
+      bound[bestIdx2] = 1;
+      match[bestIdx2] = i;
       nmatches++;
-      float rot = K.keys[i].angle - keys[bestIdx2].angle;
+      float rot = angle[i] - G.keys[bestIdx2].angle;
       if (rot < 0.0) rot += 360.0f;
       int bin = (int)std::round(rot * factor);
       if (bin == HISTO_LENGTH) bin = 0;
@@ -370,10 +374,44 @@ int MapTracker::search_by_projection_kf(const std::vector<Key>& keys,
   for (int i = 0; i < HISTO_LENGTH; i++) {
     if (i == ind1 || i == ind2 || i == ind3) continue;
     for (int j : rotHist[i]) {
-      C.mps[j] = -1;
+      match[j] = -1;
       nmatches--;
     }
   }
+  return nmatches;
+}
+
+// the keyframe's map points gathered for search_by_projection_kf_arrays
+int MapTracker::search_by_projection_kf(const std::vector<Key>& keys,
+                                        const std::vector<uint8_t>& desc, MapFrame& C,
+                                        const float* Tcw, int kf, const std::set<int>& found,
+                                        float th, int orbDist) {
+  MatchFrame G;
+  build_grid(keys, desc, C, G);
+  const OKeyFrame& K = kfs[kf];
+  const int m = (int)K.mps.size(), n = (int)keys.size();
+  std::vector<float> Xw(3 * (size_t)m + 3, 0.f), dmin(m + 1, 0.f), dmax(m + 1, 0.f), ang(m + 1, 0.f);
+  std::vector<uint8_t> pdesc(32 * (size_t)m + 32, 0), skip(m + 1, 1), bound(n + 1, 0);
+  for (int i = 0; i < m; i++) {
+    const int h = K.mps[i];
+    if (h < 0) continue;
+    const OMapPoint& p = mp(h);
+    if (p.bad || found.count(h)) continue;
+    skip[i] = 0;
+    memcpy(&Xw[3 * (size_t)i], p.pos, 12);
+    dmin[i] = p.minDist;
+    dmax[i] = p.maxDist;
+    memcpy(&pdesc[32 * (size_t)i], p.desc, 32);
+    ang[i] = K.keys[i].angle;
+  }
+  for (int k = 0; k < n; k++) bound[k] = C.mps[k] >= 0;
+  std::vector<int> match(n + 1, -1);
+  const int nmatches = search_by_projection_kf_arrays(G, Tcw, m, Xw.data(), dmin.data(),
+                                                      dmax.data(), pdesc.data(), ang.data(),
+                                                      skip.data(), th, orbDist, bound.data(),
+                                                      match.data());
+  for (int k = 0; k < n; k++)
+    if (match[k] >= 0) C.mps[k] = K.mps[match[k]];
   return nmatches;
 }
 
@@ -501,34 +539,32 @@ bool MapTracker::relocalization(const std::vector<Key>& keys, const std::vector<
 }
 
 // ORBmatcher(0.6, false)::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, false)
-int MapTracker::search_for_triangulation(int kf1, int kf2, const float* F12,
-                                         std::vector<std::pair<int, int>>& pairs) {
-  const OKeyFrame& K1 = kfs[kf1];
-  const OKeyFrame& K2 = kfs[kf2];
+int search_for_triangulation_arrays(const SftKeyFrameView& K1, const SftKeyFrameView& K2,
+                                    const float* F12, const MapCam& cam, int* m12) {
   float C2[3];
   xform(K2.Tcw, K1.Ow, C2);
   const float invz = 1.0f / C2[2];
   const float ex = cam.fx * C2[0] * invz + cam.cx;
   const float ey = cam.fy * C2[1] * invz + cam.cy;
-  std::vector<int> m12(K1.keys.size(), -1);
+  for (int i = 0; i < K1.n; i++) m12[i] = -1;
   int nmatches = 0;
-  const FeatVecO& f1 = K1.fv;
-  const FeatVecO& f2 = K2.fv;
-  size_t a = 0, b = 0;
-  while (a < f1.node.size() && b < f2.node.size()) {
+  const FeatVec& f1 = K1.fv;
+  const FeatVec& f2 = K2.fv;
+  int a = 0, b = 0;
+  while (a < f1.n_nodes && b < f2.n_nodes) {
     if (f1.node[a] == f2.node[b]) {
       for (int p = f1.start[a]; p < f1.start[a + 1]; p++) {
         const int idx1 = f1.feat[p];
-        if (K1.mps[idx1] >= 0) continue;
+        if (K1.has_mp[idx1]) continue;
         const bool bStereo1 = K1.uR[idx1] >= 0;
         const Key& kp1 = K1.keys[idx1];
-        const uint8_t* d1 = K1.desc.data() + 32 * (size_t)idx1;
+        const uint8_t* d1 = K1.desc + 32 * (size_t)idx1;
         int bestDist = TH_LOW, bestIdx2 = -1;
         for (int q = f2.start[b]; q < f2.start[b + 1]; q++) {
           const int idx2 = f2.feat[q];
-          if (K2.mps[idx2] >= 0) continue;  // vbMatched2 is never set (ORBmatcher.cc:1100)
+          if (K2.has_mp[idx2]) continue;  // vbMatched2 is never set (ORBmatcher.cc:1100)
           const bool bStereo2 = K2.uR[idx2] >= 0;
-          const int dist = descriptor_distance(d1, K2.desc.data() + 32 * (size_t)idx2);
+          const int dist = descriptor_distance(d1, K2.desc + 32 * (size_t)idx2);
           if (dist > TH_LOW || dist > bestDist) continue;
           const Key& kp2 = K2.keys[idx2];
           if (!bStereo1 && !bStereo2) {
@@ -548,14 +584,38 @@ int MapTracker::search_for_triangulation(int kf1, int kf2, const float* F12,
       a++;
       b++;
     } else if (f1.node[a] < f2.node[b]) {
-      a = (size_t)(std::lower_bound(f1.node.begin(), f1.node.end(), f2.node[b]) - f1.node.begin());
+      a = (int)(std::lower_bound(f1.node, f1.node + f1.n_nodes, f2.node[b]) - f1.node);
     } else {
-      b = (size_t)(std::lower_bound(f2.node.begin(), f2.node.end(), f1.node[a]) - f2.node.begin());
+      b = (int)(std::lower_bound(f2.node, f2.node + f2.n_nodes, f1.node[a]) - f2.node);
     }
   }
+  return nmatches;
+}
+
+int MapTracker::search_for_triangulation(int kf1, int kf2, const float* F12,
+                                         std::vector<std::pair<int, int>>& pairs) {
+  std::vector<uint8_t> has1, has2;
+  auto view = [&](int k, std::vector<uint8_t>& has) {
+    const OKeyFrame& K = kfs[k];
+    has.assign(K.keys.size() + 1, 0);
+    for (size_t i = 0; i < K.mps.size(); i++) has[i] = K.mps[i] >= 0;
+    SftKeyFrameView v;
+    v.n = (int)K.keys.size();
+    v.keys = K.keys.data();
+    v.desc = K.desc.data();
+    v.uR = K.uR.data();
+    v.has_mp = has.data();
+    v.fv = K.fv.view();
+    v.Tcw = K.Tcw;
+    v.Ow = K.Ow;
+    return v;
+  };
+  const SftKeyFrameView V1 = view(kf1, has1), V2 = view(kf2, has2);
+  std::vector<int> m12(V1.n + 1, -1);
+  const int nmatches = search_for_triangulation_arrays(V1, V2, F12, cam, m12.data());
   pairs.clear();
-  for (size_t i = 0; i < m12.size(); i++)
-    if (m12[i] >= 0) pairs.push_back({(int)i, m12[i]});
+  for (int i = 0; i < V1.n; i++)
+    if (m12[i] >= 0) pairs.push_back({i, m12[i]});
   return nmatches;
 }
 

@@ -583,3 +583,84 @@ def search_local_points(kps, desc, depth, tcw, Xw, normal, min_dist, max_dist, p
                                       _p(sc), len(sc), _p(t), m, *[_p(a) for a in arrs], _p(pd),
                                       _p(sk), th, _p(tk), _p(match), _p(frus))
     return nm, match[:len(kps)], frus[:m]
+
+
+def search_by_projection_keyframe(kps, desc, depth, tcw, Xw, min_dist, max_dist, pdesc, angle,
+                                  skip, th, orb_dist, bound, K, bf, scale):
+    """Relocalization's SearchByProjection(F, KF, sAlreadyFound, th, ORBdist): (nmatches,
+    match[cur key] = point index or -1)."""
+    L = lib()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.oracle_search_by_projection_kf.argtypes = [ci, vp, vp, vp, ci, ci, vp, vp, ci, vp, ci, vp,
+                                                 vp, vp, vp, vp, vp, ctypes.c_float, ci, vp, vp]
+    kps = np.ascontiguousarray(kps, KP_DTYPE)
+    desc = np.ascontiguousarray(desc, np.uint8)
+    depth = np.ascontiguousarray(depth, np.float32)
+    H, W = depth.shape
+    arrs = [np.ascontiguousarray(a, np.float32) for a in (Xw, min_dist, max_dist)]
+    pd = np.ascontiguousarray(pdesc, np.uint8)
+    ang = np.ascontiguousarray(angle, np.float32)
+    sk = np.ascontiguousarray(skip, np.uint8)
+    bd = np.ascontiguousarray(bound, np.uint8)
+    assert len(bd) == len(kps) and len(ang) == len(sk)
+    sc = np.ascontiguousarray(scale, np.float32)
+    t = np.ascontiguousarray(tcw, np.float32).reshape(16)
+    cam = _cam(K, bf)
+    match = np.zeros(max(len(kps), 1), np.int32)
+    nm = L.oracle_search_by_projection_kf(len(kps), _p(kps), _p(desc), _p(depth), W, H, _p(cam),
+                                          _p(sc), len(sc), _p(t), len(sk),
+                                          *[_p(a) for a in arrs], _p(pd), _p(ang), _p(sk), th,
+                                          int(orb_dist), _p(bd), _p(match))
+    return nm, match[:len(kps)]
+
+
+class _SftKF(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("keys", ctypes.c_void_p), ("desc", ctypes.c_void_p),
+                ("uR", ctypes.c_void_p), ("has_mp", ctypes.c_void_p), ("n_nodes", ctypes.c_int),
+                ("node", ctypes.c_void_p), ("start", ctypes.c_void_p), ("feat", ctypes.c_void_p),
+                ("Tcw", ctypes.c_float * 16)]
+
+
+def _sft_kf(kf, keep):
+    k = np.ascontiguousarray(kf["kps"], KP_DTYPE)
+    d = np.ascontiguousarray(kf["desc"], np.uint8)
+    u = np.ascontiguousarray(kf["uR"], np.float32)
+    h = np.ascontiguousarray(kf["has_mp"], np.uint8)
+    node, start, feat = (np.ascontiguousarray(kf["fv"][0], np.uint32),
+                         np.ascontiguousarray(kf["fv"][1], np.int32),
+                         np.ascontiguousarray(kf["fv"][2], np.int32))
+    assert len(d) == len(u) == len(h) == len(k)
+    keep += [k, d, u, h, node, start, feat]
+    s = _SftKF()
+    s.n = len(k)
+    s.keys, s.desc, s.uR, s.has_mp = k.ctypes.data, d.ctypes.data, u.ctypes.data, h.ctypes.data
+    s.n_nodes = len(node)
+    s.node, s.start, s.feat = node.ctypes.data, start.ctypes.data, feat.ctypes.data
+    s.Tcw[:] = np.asarray(kf["Tcw"], np.float32).reshape(16).tolist()
+    return s
+
+
+def search_for_triangulation(kf1, kf2s, K, bf, scale):
+    """ComputeF12 + SearchForTriangulation of kf1 against each keyframe of kf2s.  A keyframe is a
+    dict(kps, desc, uR, has_mp, fv=(node ids, starts, features), Tcw).  Returns (nmatches
+    (n_pairs), match12 (n_pairs x n1: idx2 or -1), F12 (n_pairs x 3 x 3))."""
+    L = lib()
+    vp, ci = ctypes.c_void_p, ctypes.c_int
+    L.oracle_search_for_triangulation.argtypes = [vp, vp, ci, vp, ci, vp, vp, vp, vp]
+    keep = []
+    a = _sft_kf(kf1, keep)
+    npairs = len(kf2s)
+    B = (_SftKF * max(npairs, 1))()
+    for p, kf in enumerate(kf2s):
+        B[p] = _sft_kf(kf, keep)
+    sc = np.ascontiguousarray(scale, np.float32)
+    cam = _cam(K, bf)
+    m12 = np.full((max(npairs, 1), max(a.n, 1)), -1, np.int32)
+    m12c = np.full(max(npairs, 1) * max(a.n, 1), -1, np.int32)
+    F = np.zeros((max(npairs, 1), 3, 3), np.float32)
+    nm = np.zeros(max(npairs, 1), np.int32)
+    L.oracle_search_for_triangulation(_p(cam), _p(sc), len(sc), ctypes.addressof(a), npairs,
+                                      ctypes.addressof(B), _p(m12c), _p(F), _p(nm))
+    if a.n > 0 and npairs > 0:
+        m12 = m12c[:npairs * a.n].reshape(npairs, a.n)
+    return nm[:npairs], m12[:npairs, :a.n], F[:npairs]

@@ -719,4 +719,68 @@ int oracle_search_by_bow(int kf_nodes, const uint32_t* kf_node, const int* kf_st
                        check_orientation != 0, match);
 }
 
+// Relocalization's SearchByProjection(F, KF, sAlreadyFound, th, ORBdist) probe: match (n) = the
+// point newly bound to each current key or -1; returns nmatches.
+int oracle_search_by_projection_kf(int n, const Key* keys, const uint8_t* desc, const float* depth,
+                                   int W, int H, const float* cam, const float* scale,
+                                   int nlevels, const float* Tcw, int m, const float* Xw,
+                                   const float* min_dist, const float* max_dist,
+                                   const uint8_t* pdesc, const float* angle, const uint8_t* skip,
+                                   float th, int orb_dist, const uint8_t* bound, int* match) {
+  MatchFrame C;
+  match_frame(C, n, keys, desc, depth, W, H, cam, scale, nlevels);
+  return search_by_projection_kf_arrays(C, Tcw, m, Xw, min_dist, max_dist, pdesc, angle, skip, th,
+                                        orb_dist, bound, match);
+}
+
+// One keyframe of the SearchForTriangulation probe.
+struct OracleSftKF {
+  int n;
+  const Key* keys;
+  const uint8_t* desc;
+  const float* uR;
+  const uint8_t* has_mp;
+  int n_nodes;
+  const uint32_t* node;
+  const int* start;
+  const int* feat;
+  float Tcw[16];
+};
+
+// ComputeF12 + SearchForTriangulation of kf1 against each of n_pairs neighbours: match12
+// (n_pairs x kf1.n), F12 (n_pairs x 9), nmatches (n_pairs).
+int oracle_search_for_triangulation(const float* cam, const float* scale, int nlevels,
+                                    const OracleSftKF* kf1, int n_pairs, const OracleSftKF* kf2,
+                                    int* match12, float* F12, int* nmatches) {
+  MapCam mc;
+  mc.fx = cam[0]; mc.fy = cam[1]; mc.cx = cam[2]; mc.cy = cam[3]; mc.bf = cam[4];
+  mc.nlevels = nlevels;
+  mc.scale.assign(scale, scale + nlevels);
+  float Ow1[3], Ow2[3];
+  auto view = [](const OracleSftKF* k, float* Ow) {
+    SftKeyFrameView v;
+    v.n = k->n;
+    v.keys = k->keys;
+    v.desc = k->desc;
+    v.uR = k->uR;
+    v.has_mp = k->has_mp;
+    v.fv.n_nodes = k->n_nodes;
+    v.fv.node = k->node;
+    v.fv.start = k->start;
+    v.fv.feat = k->feat;
+    v.Tcw = k->Tcw;
+    cam_centre(k->Tcw, Ow);
+    v.Ow = Ow;
+    return v;
+  };
+  const SftKeyFrameView V1 = view(kf1, Ow1);
+  for (int p = 0; p < n_pairs; p++) {
+    const SftKeyFrameView V2 = view(kf2 + p, Ow2);
+    compute_f12(V1.Tcw, V2.Tcw, mc, F12 + 9 * (size_t)p);
+    nmatches[p] = search_for_triangulation_arrays(V1, V2, F12 + 9 * (size_t)p, mc,
+                                                  match12 + (size_t)p * (size_t)V1.n);
+  }
+  return 0;
+}
+
 }  // extern "C"

@@ -181,6 +181,33 @@ std::vector<int> kf_features_in_area(const OKeyFrame& K, const MapCam& cam, floa
 int fuse_candidate(const OKeyFrame& K, const MapCam& cam, const OMapPoint& p, float th,
                    int* bestIdx);
 
+// ---- the vocabulary path's two matchers over arrays (bowmap_ref.cpp)
+// ORBmatcher(0.9, true)::SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist)
+// (ORBmatcher.cc:2104-2231) over the keyframe's m map points in mvpMapPoints order: skip[j] = bad
+// or already found, angle[j] = the keyframe key's; bound[k] (G.n) = current key k holds a MapPoint
+// when the call starts.  match[k] = the point newly bound to key k, or -1.  Returns nmatches.
+int search_by_projection_kf_arrays(const MatchFrame& G, const float* Tcw, int m, const float* Xw,
+                                   const float* min_dist, const float* max_dist,
+                                   const uint8_t* pdesc, const float* angle, const uint8_t* skip,
+                                   float th, int orbDist, const uint8_t* bound, int* match);
+// A keyframe as SearchForTriangulation reads it.
+struct SftKeyFrameView {
+  int n = 0;
+  const Key* keys = nullptr;
+  const uint8_t* desc = nullptr;
+  const float* uR = nullptr;
+  const uint8_t* has_mp = nullptr;  // mvpMapPoints[i] != NULL
+  FeatVec fv;
+  const float* Tcw = nullptr;
+  const float* Ow = nullptr;
+};
+// ORBmatcher(0.6, false)::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, false)
+// (ORBmatcher.cc:1032-1198): match12[idx1] (K1.n) = idx2 or -1.  Returns nmatches.
+int search_for_triangulation_arrays(const SftKeyFrameView& K1, const SftKeyFrameView& K2,
+                                    const float* F12, const MapCam& cam, int* match12);
+// LocalMapping::ComputeF12 (LocalMapping.cc:540-557)
+void compute_f12(const float* T1, const float* T2, const MapCam& cam, float F[9]);
+
 class MapTracker {
  public:
   void init(const MapCam& cam);

@@ -58,6 +58,10 @@ def test_load_vocabulary_errors(tmp_path):
         p.write_text("10 12 0 0\n")  # L > 10 (TemplatedVocabulary.h:1359)
         with pytest.raises(RuntimeError):
             ctx.load_vocabulary(str(p))
+        p = tmp_path / "header_only.txt"
+        p.write_text("10 6 0 0\n")  # a root without children: no word to descend to
+        with pytest.raises(RuntimeError):
+            ctx.load_vocabulary(str(p))
         ctx.load_vocabulary(VOC)
     finally:
         ctx.close()
