@@ -373,7 +373,8 @@ int mmt_search_local_points(mmt_ctx* ctx, const mmt_match_frame* cur,
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned int>>, FeatureVector.h) as flat
  * arrays: node_id ascending; the features of node k are feat[node_start[k] .. node_start[k+1])
  * in insertion order.  Every frame feature is listed in at most one node (DBoW2's transform puts
- * each feature in one node at the direct-index level), and a node holds at most 2048 of them. */
+ * each feature in one node at the direct-index level), and a node holds at most 16384 of them
+ * (a vocabulary of depth <= 4 files every feature of a frame under node 0). */
 typedef struct mmt_feature_vector {
   int n_nodes;
   const uint32_t* node_id;    /* n_nodes              */

@@ -345,13 +345,17 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
   const int nn1 = (int)K.fv.node.size(), nf1 = (int)K.fv.feat.size();
   const int nn2 = (int)C.fv.node.size(), nf2 = (int)C.fv.feat.size();
   for (int q = 0; q < nn2; q++)
-    if (C.fv.start[q + 1] - C.fv.start[q] > kBowMaxNodeFeatures)
-      throw ArgError("SearchByBoW: a vocabulary node holds more than 2048 frame features");
+    if (C.fv.start[q + 1] - C.fv.start[q] > kMaxMatchKeys)
+      throw ArgError("SearchByBoW: a vocabulary node holds more than 16384 frame features");
+  std::vector<int2> wide;  // k_bow_nodes_wide's nodes (none allocates nothing)
+  bow_wide_pairs(K.fv.node.data(), nn1, C.fv.node.data(), C.fv.start.data(), nn2, wide);
+  const int nw = (int)wide.size();
   const size_t o_ok = 0, o_n1 = al16(nk), o_s1 = o_n1 + al16(4 * (size_t)nn1),
                o_f1 = o_s1 + al16(4 * (size_t)(nn1 + 1)), o_n2 = o_f1 + al16(4 * (size_t)nf1),
                o_s2 = o_n2 + al16(4 * (size_t)nn2), o_f2 = o_s2 + al16(4 * (size_t)(nn2 + 1)),
-               o_up = o_f2 + al16(4 * (size_t)nf2), o_m = o_up, o_h = o_m + al16(4 * (size_t)nF),
-               o_c = o_h + al16(4 * 32), tot = o_c + 16;
+               o_w = o_f2 + al16(4 * (size_t)nf2), o_up = o_w + al16(sizeof(int2) * (size_t)nw),
+               o_m = o_up, o_h = o_m + al16(4 * (size_t)nF), o_c = o_h + al16(4 * 32),
+               tot = o_c + 16;
   bw_grow(tot);
   uint8_t* h = h_bw_;
   for (int i = 0; i < nk; i++) h[o_ok + i] = K.mps[i] >= 0 && !pts_[K.mps[i]].bad;
@@ -361,6 +365,7 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
   memcpy(h + o_n2, C.fv.node.data(), 4 * (size_t)nn2);
   memcpy(h + o_s2, C.fv.start.data(), 4 * (size_t)(nn2 + 1));
   memcpy(h + o_f2, C.fv.feat.data(), 4 * (size_t)nf2);
+  if (nw) memcpy(h + o_w, wide.data(), sizeof(int2) * (size_t)nw);
   MMT_HIP(hipMemcpyAsync(d_bw_, h_bw_, o_up, hipMemcpyHostToDevice, s_));
   uint8_t* d = d_bw_;
   const BowFeatVec a{nn1, (const uint32_t*)(d + o_n1), (const int*)(d + o_s1),
@@ -368,7 +373,8 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
   const BowFeatVec b{nn2, (const uint32_t*)(d + o_n2), (const int*)(d + o_s2),
                      (const int*)(d + o_f2)};
   launch_search_by_bow(a, K.dev.keys, K.dev.desc, d + o_ok, b, G.keys, G.desc, nF, nnratio, 1,
-                       (int*)(d + o_m), (int*)(d + o_h), (int*)(d + o_c), s_);
+                       (int*)(d + o_m), (int*)(d + o_h), (int*)(d + o_c), (const int2*)(d + o_w),
+                       nw, s_);
   MMT_HIP(hipMemcpyAsync(h + o_m, d + o_m, tot - o_m, hipMemcpyDeviceToHost, s_));
   MMT_HIP(hipStreamSynchronize(s_));
   match.assign((int*)(h + o_m), (int*)(h + o_m) + nF);

@@ -713,7 +713,7 @@ static void check_feature_vector(const mmt_feature_vector* v, int n, std::vector
     if (k > 0 && !(v->node_id[k - 1] < v->node_id[k])) throw ArgError("node ids not ascending");
     const int a = v->node_start[k], b = v->node_start[k + 1];
     if (b < a) throw ArgError("node_start not monotone");
-    if (b - a > max_node) throw ArgError("a vocabulary node holds more than 2048 frame features");
+    if (b - a > max_node) throw ArgError("a vocabulary node holds more than 16384 frame features");
     for (int q = a; q < b; q++) {
       const int f = v->feat[q];
       if (f < 0 || f >= n) throw ArgError("feature index out of range");
@@ -975,7 +975,11 @@ int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const
   return guard(ctx, [&] {
     check_feature_vector(&kf->fv, kf->n, nullptr, INT32_MAX);
     std::vector<uint8_t> once((size_t)std::max(n_cur, 1), 0);
-    check_feature_vector(cur_fv, n_cur, &once, mmt::kBowMaxNodeFeatures);
+    check_feature_vector(cur_fv, n_cur, &once, mmt::kMaxMatchKeys);
+    std::vector<int2> wide;  // the nodes of k_bow_nodes_wide
+    if (kf->fv.n_nodes > 0 && cur_fv->n_nodes > 0)
+      mmt::bow_wide_pairs(kf->fv.node_id, kf->fv.n_nodes, cur_fv->node_id, cur_fv->node_start,
+                          cur_fv->n_nodes, wide);
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     hipStream_t s = ctx->stream;
     const int nk = kf->n, nkn = kf->fv.n_nodes, nfn = cur_fv->n_nodes;
@@ -986,9 +990,11 @@ int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const
     DevBuf<uint32_t> kn(nkn), fnode(nfn);
     DevBuf<int> ks(nkn + 1), kfe(nkfeat), fs(nfn + 1), ffe(nffeat);
     DevBuf<int> match(n_cur), hist(32), cnt(2);
+    DevBuf<int2> wd(wide.size());
     auto up = [&](void* d, const void* h, size_t bytes) {
       if (bytes) MMT_HIP(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, s));
     };
+    up(wd.p, wide.data(), sizeof(int2) * wide.size());
     up(kk.p, kf->kps, sizeof(mmt_kp) * (size_t)nk);
     up(kd.p, kf->desc, 32 * (size_t)nk);
     up(ok.p, kf->mp_valid, (size_t)nk);
@@ -1006,7 +1012,8 @@ int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const
     }
     mmt::BowFeatVec a{nkn, kn.p, ks.p, kfe.p}, b{nfn, fnode.p, fs.p, ffe.p};
     mmt::launch_search_by_bow(a, kk.p, kd.p, ok.p, b, fk.p, fd.p, n_cur, nn_ratio,
-                              check_orientation, match.p, hist.p, cnt.p, s);
+                              check_orientation, match.p, hist.p, cnt.p, wd.p, (int)wide.size(),
+                              s);
     if (n_cur > 0)
       MMT_HIP(hipMemcpyAsync(match_out, match.p, 4 * (size_t)n_cur, hipMemcpyDeviceToHost, s));
     MMT_HIP(hipMemcpyAsync(nmatches, cnt.p + 1, 4, hipMemcpyDeviceToHost, s));

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <vector>
 
 #include "../../include/mmt.h"
 
@@ -127,13 +128,21 @@ struct BowFeatVec {
   const int* start;  // n_nodes + 1
   const int* feat;
 };
-constexpr int kBowMaxNodeFeatures = 64 * 32;  // frame features one node may hold (lane bitmasks)
+// frame features of a node the one-wave kernel takes (lane bitmasks); a node above it, up to
+// kMaxMatchKeys, is a wide node and goes to the workgroup-wide kernel
+constexpr int kBowMaxNodeFeatures = 64 * 32;
+// The (keyframe node index, frame node index) pairs of the common nodes whose frame node is
+// wide, from the host copies of the two node lists (ids ascending).
+void bow_wide_pairs(const uint32_t* kf_node, int n_kf_nodes, const uint32_t* f_node,
+                    const int* f_start, int n_f_nodes, std::vector<int2>& out);
 // match (nF ints) receives the keyframe key index per frame key or -1, hist 30 ints and
-// counters 2 ints of scratch; counters[1] = nmatches after the launch.
+// counters 2 ints of scratch; counters[1] = nmatches after the launch.  wide: bow_wide_pairs'
+// n_wide pairs in device memory (no frame node may hold more than kMaxMatchKeys features).
 void launch_search_by_bow(const BowFeatVec& kf, const mmt_kp* kf_keys, const uint8_t* kf_desc,
                           const uint8_t* kf_ok, const BowFeatVec& f, const mmt_kp* f_keys,
                           const uint8_t* f_desc, int nF, float nnratio, int check_orientation,
-                          int* match, int* hist, int* counters, hipStream_t st);
+                          int* match, int* hist, int* counters, const int2* wide, int n_wide,
+                          hipStream_t st);
 
 // The edge list of Optimizer::PoseOptimization (Optimizer.cc:3160-3230) built on the device from a
 // matcher's output, in key order: key i is an edge when match[i] >= 0 (position src_X[match[i]],

@@ -1008,7 +1008,8 @@ __global__ __launch_bounds__(256) void k_bow_nodes(BowArgs a) {
   }
   if (lo >= a.f.n_nodes || a.f.node[lo] != id) return;
   const int fb = a.f.start[lo], fn = a.f.start[lo + 1] - fb;
-  const int nch = (fn + 63) >> 6;  // <= 32 (host-checked)
+  if (fn > kBowMaxNodeFeatures) return;  // wave-uniform: k_bow_nodes_wide's node
+  const int nch = (fn + 63) >> 6;  // <= 32
   // this lane's frame features (positions lane + 64 c) and their descriptors stay in L1/L2; the
   // matched flags live in a register bitmask
   uint32_t taken = 0;
@@ -1053,6 +1054,161 @@ __global__ __launch_bounds__(256) void k_bow_nodes(BowArgs a) {
     nm++;
   }
   if (lane == 0 && nm) atomicAdd(&a.counters[0], nm);
+}
+
+// A frame node of more than kBowMaxNodeFeatures features (a vocabulary of depth <= 4 files every
+// feature under node 0): one 512-thread workgroup per (keyframe node, frame node) pair of the
+// host's list, the same replay.  Thread t owns positions t + 512 c (c < 32: kMaxMatchKeys), their
+// feature indices and matched flags in registers, and the descriptors of its first eight
+// positions too (a node of up to 4096 features, a 4000-feature frame, is scored without a load);
+// the other positions' descriptors are re-read from L2 every step, four per thread in flight.  A
+// matched or missing position scores as kBowNone (distance 256), so the scan is branch-free.
+// (smallest key, second-smallest distance) pairs merge as min / min-of-seconds-and-larger-key:
+// across a wave by butterfly, the 8 waves' pairs through LDS, merged again by every thread.  The
+// LDS slots alternate between replay steps, so one barrier per step orders them: a wave rewrites
+// a slot only past the next step's barrier, which every reader has reached.  The keyframe side
+// (index, MapPoint flag, descriptor) is staged in LDS 512 features at a time, one per thread, so
+// the replay waits for no global load of its own; the rotation histogram is filled after the
+// replay.  Every `continue` is taken by the whole workgroup (no barrier diverges).
+// The step is bound by its own chain (LDS read, popcounts, six butterfly rounds, barrier, merge),
+// not by occupancy: 8 waves beat 16 because the per-wave reduce and merge are half as many.
+constexpr int kBowWideThreads = 512, kBowWideWaves = kBowWideThreads / 64;
+constexpr int kBowWideChunks = kMaxMatchKeys / kBowWideThreads;
+constexpr int kBowWideRegChunks = 8, kBowWideBatch = 4, kBowWideTile = kBowWideThreads;
+constexpr uint32_t kBowNone = (256u << 16) | 0xFFFFu;  // above every key, distance 256
+static_assert(kBowWideChunks <= 32 && kMaxMatchKeys < 0xFFFF, "flag mask / 16-bit position");
+static_assert((kBowWideChunks - kBowWideRegChunks) % kBowWideBatch == 0, "whole batches");
+
+// (k1, d2) = the two smallest of {k1, d2's key, key}: smallest key, second-smallest distance
+__device__ __forceinline__ void bow_merge(uint32_t key, int second, uint32_t& k1, int& d2) {
+  const uint32_t hi = max(k1, key);
+  k1 = min(k1, key);
+  d2 = min(min(d2, second), (int)(hi >> 16));
+}
+
+// a value every lane holds alike, moved to a scalar register
+__device__ __forceinline__ uint32_t bow_uniform(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+}
+
+__device__ __forceinline__ uint32_t bow_key(const uint32_t (&dk)[8], const uint32_t (&df)[8],
+                                            bool taken, int p) {
+  int dist = 0;
+#pragma unroll
+  for (int w = 0; w < 8; w++) dist += __popc(dk[w] ^ df[w]);
+  return taken ? kBowNone : (((uint32_t)dist << 16) | (uint32_t)p);
+}
+
+__global__ __launch_bounds__(kBowWideThreads) void k_bow_nodes_wide(BowArgs a,
+                                                                    const int2* __restrict__ wide) {
+  __shared__ uint2 s_w[2][kBowWideWaves];
+  __shared__ uint4 s_dk[kBowWideTile][2];  // the tile's keyframe descriptors
+  __shared__ int s_ikf[kBowWideTile];      // and key indices (-1: no good MapPoint, skipped)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int2 pr = wide[blockIdx.x];
+  const int k = pr.x;
+  const int fb = a.f.start[pr.y], fn = a.f.start[pr.y + 1] - fb;  // <= kMaxMatchKeys (host)
+  const int nch = (fn + kBowWideThreads - 1) / kBowWideThreads;
+  int fi[kBowWideChunks];
+  uint32_t taken = 0;  // bit c: position tid + 512 c is matched (or past the node's end)
+#pragma unroll
+  for (int c = 0; c < kBowWideChunks; c++) {
+    const int p = tid + kBowWideThreads * c;
+    if (p < fn) {
+      fi[c] = a.f.feat[fb + p];
+    } else {
+      fi[c] = 0;
+      taken |= 1u << c;
+    }
+  }
+  // a position past the end reads feature 0's descriptor (fn > 0) and scores kBowNone
+  uint32_t dc[kBowWideRegChunks][8];
+#pragma unroll
+  for (int c = 0; c < kBowWideRegChunks; c++) load_desc8(a.f_desc + 32 * (size_t)fi[c], dc[c]);
+  const int q0 = a.kf.start[k], q1 = a.kf.start[k + 1];
+  int nm = 0, par = 0;
+  for (int t0 = q0; t0 < q1; t0 += kBowWideTile) {
+    const int nt = min(kBowWideTile, q1 - t0);
+    __syncthreads();  // the previous tile is replayed
+    if (tid < nt) {
+      const int i = a.kf.feat[t0 + tid];
+      const bool ok = a.kf_ok[i] != 0;  // pMP != NULL and !isBad()
+      s_ikf[tid] = ok ? i : -1;
+      if (ok) {
+        const uint4* d = reinterpret_cast<const uint4*>(a.kf_desc + 32 * (size_t)i);
+        s_dk[tid][0] = d[0];
+        s_dk[tid][1] = d[1];
+      }
+    }
+    __syncthreads();
+    for (int j = 0; j < nt; j++) {
+      const int ikf = __builtin_amdgcn_readfirstlane(s_ikf[j]);
+      if (ikf < 0) continue;
+      const uint4 da = s_dk[j][0], db = s_dk[j][1];
+      const uint32_t dk[8] = {bow_uniform(da.x), bow_uniform(da.y), bow_uniform(da.z),
+                              bow_uniform(da.w), bow_uniform(db.x), bow_uniform(db.y),
+                              bow_uniform(db.z), bow_uniform(db.w)};
+      uint32_t k1 = kBowNone;  // thread-local smallest (dist << 16 | position)
+      int d2 = 256;            // thread-local second-smallest distance
+#pragma unroll
+      for (int c = 0; c < kBowWideRegChunks; c++) {
+        if (c >= nch) break;
+        bow_merge(bow_key(dk, dc[c], (taken >> c) & 1u, tid + kBowWideThreads * c), 256, k1, d2);
+      }
+#pragma unroll
+      for (int cb = kBowWideRegChunks; cb < kBowWideChunks; cb += kBowWideBatch) {
+        if (cb >= nch) break;
+        uint32_t df[kBowWideBatch][8];
+#pragma unroll
+        for (int b = 0; b < kBowWideBatch; b++)
+          load_desc8(a.f_desc + 32 * (size_t)fi[cb + b], df[b]);
+#pragma unroll
+        for (int b = 0; b < kBowWideBatch; b++)
+          bow_merge(bow_key(dk, df[b], (taken >> (cb + b)) & 1u,
+                            tid + kBowWideThreads * (cb + b)), 256, k1, d2);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t pk = (uint32_t)__shfl_xor((int)k1, o, 64);
+        const int pd = __shfl_xor(d2, o, 64);
+        bow_merge(pk, pd, k1, d2);
+      }
+      uint2* slot = s_w[par];
+      par ^= 1;
+      if (lane == 0) slot[wave] = make_uint2(k1, (uint32_t)d2);
+      __syncthreads();
+      uint32_t m1 = kBowNone;
+      int best2 = 256;
+#pragma unroll
+      for (int w = 0; w < kBowWideWaves; w++) {
+        const uint2 e = slot[w];
+        bow_merge(e.x, (int)e.y, m1, best2);
+      }
+      const int best1 = (int)(m1 >> 16);  // 256 when nothing is left
+      if (best1 > TH_LOW || !((float)best1 < a.ratio * (float)best2)) continue;
+      const int p = (int)(m1 & 0xFFFFu);
+      if (tid == (p & (kBowWideThreads - 1))) {
+        int iF = 0;
+#pragma unroll
+        for (int c = 0; c < kBowWideChunks; c++)
+          if (c == p / kBowWideThreads) iF = fi[c];
+        taken |= 1u << (p / kBowWideThreads);
+        a.match[iF] = ikf;
+      }
+      nm++;
+    }
+  }
+  if (tid == 0 && nm) atomicAdd(&a.counters[0], nm);
+  // the rotation histogram after the replay (its loads are off the replay's critical path): a
+  // thread's matched positions are its flags below the node's end, match[] its own stores
+  if (a.check_orientation) {
+#pragma unroll
+    for (int c = 0; c < kBowWideChunks; c++) {
+      if (tid + kBowWideThreads * c >= fn || !((taken >> c) & 1u)) continue;
+      const int ikf = a.match[fi[c]];
+      atomicAdd(&a.hist[rot_bin(a.kf_keys[ikf].angle, a.f_keys[fi[c]].angle)], 1);
+    }
+  }
 }
 
 // the rotation-consistency filter of SearchByBoW (ORBmatcher.cc:641-660) and nmatches
@@ -1102,10 +1258,27 @@ __global__ __launch_bounds__(256) void k_bow_rot(BowArgs a) {
   if (tid == 0) a.counters[1] = a.counters[0] - s_removed;
 }
 
+void bow_wide_pairs(const uint32_t* kf_node, int n_kf_nodes, const uint32_t* f_node,
+                    const int* f_start, int n_f_nodes, std::vector<int2>& out) {
+  out.clear();
+  for (int i = 0, j = 0; i < n_kf_nodes && j < n_f_nodes;) {
+    if (kf_node[i] < f_node[j]) {
+      i++;
+    } else if (f_node[j] < kf_node[i]) {
+      j++;
+    } else {
+      if (f_start[j + 1] - f_start[j] > kBowMaxNodeFeatures) out.push_back(make_int2(i, j));
+      i++;
+      j++;
+    }
+  }
+}
+
 void launch_search_by_bow(const BowFeatVec& kf, const mmt_kp* kf_keys, const uint8_t* kf_desc,
                           const uint8_t* kf_ok, const BowFeatVec& f, const mmt_kp* f_keys,
                           const uint8_t* f_desc, int nF, float nnratio, int check_orientation,
-                          int* match, int* hist, int* counters, hipStream_t st) {
+                          int* match, int* hist, int* counters, const int2* wide, int n_wide,
+                          hipStream_t st) {
   BowArgs a;
   a.kf = kf;
   a.f = f;
@@ -1125,6 +1298,10 @@ void launch_search_by_bow(const BowFeatVec& kf, const mmt_kp* kf_keys, const uin
   MMT_HIP(hipMemsetAsync(counters, 0, sizeof(int) * 2, st));
   if (kf.n_nodes > 0 && f.n_nodes > 0) {
     hipLaunchKernelGGL(k_bow_nodes, dim3((kf.n_nodes + 3) / 4), dim3(256), 0, st, a);
+    MMT_HIP(hipGetLastError());
+  }
+  if (n_wide > 0) {
+    hipLaunchKernelGGL(k_bow_nodes_wide, dim3(n_wide), dim3(kBowWideThreads), 0, st, a, wide);
     MMT_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(k_bow_rot, dim3(1), dim3(256), 0, st, a);
