@@ -1,31 +1,39 @@
 // multimot_track_amd/csrc/mmt_ba.hip -- the solve of Optimizer::LocalBundleAdjustment (reference
-// src/Optimizer.cc:3394-3665) as ONE persistent 512-thread workgroup: both rounds
-// (optimize(5) with Huber kernels, the level-1 split of bad edges, optimize(10) without kernels),
-// every LM iteration and trial, and the final erase test, with no host round trip.
+// src/Optimizer.cc:3394-3665): both rounds (optimize(5) with Huber kernels, the
+// level-1 split of bad edges, optimize(10) without kernels), every LM iteration and trial, and the
+// final erase test.
 //
 // g2o semantics restated (the CPU checker is oracle/ba_ref.cpp):
 //   EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ computeError, linearizeOplus (types_six_dof_expmap
 //   .h:91-141, .cpp:103-234); constructQuadraticForm with rho' Omega (base_binary_edge.hpp:55-115);
 //   BlockSolver_6_3 Schur complement over the points (block_solver.hpp:406-489);
-//   OptimizationAlgorithmLevenberg::solve (lambda init tau * max diagonal, rho, the 2/3 - 1/3 lambda
-//   update, 10 trials, Raul's stop) and SparseOptimizer::optimize's chi2-increase stop; the solver's
-//   x persists across trials (a failed solve re-applies the previous one); edges set to level 1
-//   keep the error of their last evaluation.
+//   OptimizationAlgorithmLevenberg::solve and SparseOptimizer::optimize's stops (the LM step
+//   policy: mmt_lmstep.h); the solver's x persists across trials (a failed solve re-applies the
+//   previous one); edges set to level 1 keep the error of their last evaluation.
 //
-// Work split (sizes of the synthetic C3 sequence: ~3,500 edges, ~3,000 points, ~6 keyframes):
-//   * linearisation, point pass: one thread per point walks its edges (CSR, edge order) and keeps
-//     the 3x3 H_ll / b_l in registers; it stores each edge's H_pl block (6x3);
-//   * linearisation, keyframe pass: one wave per optimised keyframe sums J_p^T w J_p / J_p^T w e over
-//     its edges (lanes strided, 27 register sums, DPP wave sums): fixed order, no atomics;
-//   * Schur complement: per point D^-1 = (H_ll + lambda I)^-1 (Eigen's cofactor inverse), and per
-//     edge Y = H_pl D^-1 and H_pl D^-1 b_l; then one wave per keyframe-pair block sums its
-//     (edge, edge) triples (36 register sums per lane);
-//   * the reduced camera system (6 x optimised keyframes) in LDS, LDL^T left-looking in the CPU
-//     checker's operation order (one row per lane, one wave while it has at most 64 rows), the
-//     substitutions on one lane;
-//   * increments, update, errors, chi2 and the scale term per point / keyframe / edge.
-// Every reduction runs in a fixed order, so the kernel is deterministic; it agrees with the CPU
-// checker to rounding (sums in another association).  FP64 throughout; no MFMA (6x6 / 3x3 blocks).
+// The LM is spread over the chip: one LM trial is a chain of short kernels on the caller's stream
+// (points, keyframe-pair blocks and keyframes in parallel; the reduced camera system and the LM
+// decision in one workgroup each), with the LM state in device memory (BAState).  The host
+// enqueues trials in batches and reads the state's done flag after each batch; every kernel of a
+// finished solve returns at once.  (The first version ran the whole solve in one workgroup:
+// 10-11 ms per local BA of the C3 sequence; spread, a trial costs a few microseconds per kernel.)
+//   per iteration (need_lin):  k_ba2_lin   one thread per point: errors, robust chi2, H_ll, b_l,
+//                                          H_pl and the edge's pose terms (J_p^T w J_p, J_p^T w e)
+//                              k_ba2_kfsum one workgroup per optimised keyframe: H_pp, b_p; one
+//                                          per 256 points: k_ba2_lin's chi2 and diagonal partials
+//   per trial:                 k_ba2_p1    one thread per point: (H_ll + lambda I)^-1, Y, H_pl D^-1 b_l
+//                              k_ba2_p2    one workgroup per keyframe-pair block / keyframe: Schur sums
+//                              k_ba2_p3    one workgroup: the reduced system, LDL^T, increments, trial poses
+//                              k_ba2_p4    one thread per point: point increments, trial errors, chi2;
+//                                          its last workgroup then takes the LM decision (rho,
+//                                          lambda, Raul's stop, the chi2-increase stop) and the
+//                                          iteration and round bookkeeping (ba2_decide)
+// ("One thread per point": a point with more than kBaHeavy edges gets a wave instead, in the
+// workgroups that follow the thread-per-point ones in the same grid.)
+// The estimates are double-buffered (current / trial, swapped on acceptance), so a rejected trial
+// needs no restore.  Every reduction has a fixed order, so the solve is deterministic; it agrees
+// with the CPU checker to rounding (sums in another association).  FP64 throughout; no MFMA
+// (6x6 / 3x3 blocks).
 
 #include <hip/hip_runtime.h>
 
@@ -41,63 +49,13 @@
 #include "mmt_ba.h"
 #include "mmt_devmath.h"
 #include "mmt_internal.h"
+#include "mmt_lmstep.h"
 
 namespace mmt {
 
 namespace {
 
-constexpr int kBAThreads = 512;
-constexpr int kBAWaves = kBAThreads / 64;
 constexpr int kLdsRows = 96;  // reduced systems of up to 16 optimised keyframes live in LDS
-
-struct BAWork {  // global scratch (doubles unless noted), carved from d.ws
-  DSE3* pose;
-  DSE3* pose_b;
-  double* X;     // 3 n_pt
-  double* Xb;
-  double* Hll;   // 9 n_pt
-  double* bl;    // 3 n_pt
-  double* Dinv;  // 9 n_pt
-  double* err;   // 3 n_edge
-  double* Hpl;   // 18 n_edge
-  double* Y;     // 18 n_edge
-  double* cv;    // 6 n_edge
-  double* Hpp;   // 36 n_opt
-  double* bp;    // 6 n_opt
-  double* x;     // 6 n_opt + 3 n_pt (g2o's _x: poses, then points)
-  double* S;     // n6 x n6 (when the system does not fit in LDS)
-  double* vec;   // 3 n6: bs, D, y (idem)
-  uint8_t* level;  // n_edge
-  uint8_t* kf_act; // n_kf: keyframe has an active edge this round
-  uint8_t* pt_act; // n_pt
-};
-
-__device__ BAWork carve(const BADesc& d) {
-  BAWork w;
-  double* p = d.ws;
-  const size_t n6 = 6 * (size_t)d.n_opt;
-  w.pose = reinterpret_cast<DSE3*>(p); p += 7 * (size_t)d.n_kf;
-  w.pose_b = reinterpret_cast<DSE3*>(p); p += 7 * (size_t)d.n_kf;
-  w.X = p; p += 3 * (size_t)d.n_pt;
-  w.Xb = p; p += 3 * (size_t)d.n_pt;
-  w.Hll = p; p += 9 * (size_t)d.n_pt;
-  w.bl = p; p += 3 * (size_t)d.n_pt;
-  w.Dinv = p; p += 9 * (size_t)d.n_pt;
-  w.err = p; p += 3 * (size_t)d.n_edge;
-  w.Hpl = p; p += 18 * (size_t)d.n_edge;
-  w.Y = p; p += 18 * (size_t)d.n_edge;
-  w.cv = p; p += 6 * (size_t)d.n_edge;
-  w.Hpp = p; p += 36 * (size_t)d.n_opt;
-  w.bp = p; p += 6 * (size_t)d.n_opt;
-  w.x = p; p += n6 + 3 * (size_t)d.n_pt;
-  w.S = p; p += n6 * n6;
-  w.vec = p; p += 3 * n6;
-  uint8_t* b = reinterpret_cast<uint8_t*>(p);
-  w.level = b; b += d.n_edge;
-  w.kf_act = b; b += d.n_kf;
-  w.pt_act = b;
-  return w;
-}
 
 struct Cam {
   double fx, fy, cx, cy, bf;
@@ -135,6 +93,8 @@ __device__ __forceinline__ double edge_chi2(const double* e, double s, bool ster
   return stereo ? s * (e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) : s * (e[0] * e[0] + e[1] * e[1]);
 }
 
+// g2o's RobustKernelHuber with sqrt and a division, as the CPU checker has it (mmt_lm.hip's huber
+// takes rsqrt and Newton steps instead: within an ulp, not the same bits, so the two stay apart)
 __device__ __forceinline__ void huber_rho(double e, double delta, double& r0, double& r1) {
   const double dsqr = delta * delta;
   if (e <= dsqr) {
@@ -224,64 +184,6 @@ __device__ __forceinline__ void inverse3(const double (&m)[9], double (&r)[9]) {
 #undef COF
 }
 
-// workgroup sum / max of one double per thread, identical in every thread (fixed order)
-__device__ __forceinline__ double wg_sum1(double v, double* part) {
-  v = wave_sum_dpp(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) part[wave] = v;
-  __syncthreads();
-  double s = 0;
-#pragma unroll
-  for (int w = 0; w < kBAWaves; w++) s += part[w];
-  __syncthreads();
-  return s;
-}
-
-__device__ __forceinline__ double wg_max1(double v, double* part) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) part[wave] = v;
-  __syncthreads();
-  double m = 0;
-#pragma unroll
-  for (int w = 0; w < kBAWaves; w++) m = fmax(m, part[w]);
-  __syncthreads();
-  return m;
-}
-
-__device__ __forceinline__ void wave_sync_lds() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-}  // namespace
-
-namespace {
-// ================================================================== multi-kernel solve
-// The local BA's LM spread over the chip: one LM trial is a chain of short kernels on the
-// caller's stream (points, keyframe-pair blocks and keyframes in parallel; the reduced camera
-// system and the LM decision in one workgroup each), with the LM state in device memory.  The host
-// enqueues trials in batches and reads the state's done flag after each batch; every kernel of a
-// finished solve returns at once.  Round 4's first version ran the whole solve in one workgroup
-// (10-11 ms per local BA of the C3 sequence); spread, a trial costs a few microseconds per kernel.
-//   per iteration (need_lin):  k_ba2_lin   one thread per point: errors, robust chi2, H_ll, b_l,
-//                                          H_pl and the edge's pose terms (J_p^T w J_p, J_p^T w e)
-//                              k_ba2_kfsum one workgroup per optimised keyframe: H_pp, b_p; one
-//                                          per 256 points: k_ba2_lin's chi2 and diagonal partials
-//   per trial:                 k_ba2_p1    one thread per point: (H_ll + lambda I)^-1, Y, H_pl D^-1 b_l
-//                              k_ba2_p2    one workgroup per keyframe-pair block / keyframe: Schur sums
-//                              k_ba2_p3    one workgroup: the reduced system, LDL^T, increments, trial poses
-//                              k_ba2_p4    one thread per point: point increments, trial errors, chi2;
-//                                          its last workgroup then takes the LM decision (rho,
-//                                          lambda, Raul's stop, the chi2-increase stop) and the
-//                                          iteration and round bookkeeping (ba2_decide)
-// ("One thread per point": a point with more than kBaHeavy edges gets a wave instead, in the
-// workgroups that follow the thread-per-point ones in the same grid.)
-// The estimates are double-buffered (current / trial, swapped on acceptance), so a rejected trial
-// needs no restore.  Every reduction has a fixed order: the solve is deterministic.
-
 constexpr int kMkThreads = 256;
 constexpr int kMkWaves = kMkThreads / 64;
 constexpr int kMkSolveThreads = 512;
@@ -298,10 +200,11 @@ constexpr int kPtWaves = kPtThreads / 64;
 static_assert(kPtThreads % 64 == 0 && kPtThreads >= 64 && kPtThreads <= 1024, "whole waves");
 
 struct BAState {
-  int done, round, iter, qmax, need_lin, lam_init, cb, ok2, nBad, nact;
+  int done, round, iter, need_lin, lam_init, cb, ok2, nact;
   int spec_ok;  // the last trial was accepted: k_ba2_p4 linearised at it, no k_ba2_lin needed
   int it_done[2], trials[2];
-  double lambda, ni, chk, currentChi, iniChi, scale_p;
+  LMStep lm;  // lambda, ni, the chi2s and the stop counters (mmt_lmstep.h)
+  double scale_p;
   long long prof[8];  // k_ba2_p3 phase times (wall clock ticks, 100 MHz), summed over trials
 };
 
@@ -386,8 +289,6 @@ __device__ __forceinline__ double wg_maxN(double v, double* part) {
   return m;
 }
 
-// computeLambdaInit over the round's vertices: 1e-5 x the largest diagonal entry of the active
-// optimised keyframes' H_pp and the active points' H_ll (the latter from k_ba2_lin's partials)
 // the upper-triangle index of H_pp entry (r, r) in the 21 pose terms (rows r0, columns c0 >= r0)
 __device__ __forceinline__ int ba2_diag_q(int r) { return 6 * r - r * (r - 1) / 2; }
 
@@ -413,9 +314,11 @@ __device__ __forceinline__ double ba2_hsum(const BAWork2& w, int a, int q) {
   return ordered_sum(w.Hpart + q, 27, w.kitem_start[a], w.kitem_start[a + 1]);
 }
 
+// computeLambdaInit's maximum over the round's vertices: the largest diagonal entry of the active
+// optimised keyframes' H_pp and the active points' H_ll (the latter from k_ba2_lin's partials);
 // computed by wave 0 (lanes over the point workgroups and the (keyframe, diagonal) pairs) and
 // returned to every thread of the workgroup through `sh` (one barrier)
-__device__ __forceinline__ double ba2_lambda_init(const BADesc& d, const BAWork2& w, double* sh) {
+__device__ __forceinline__ double ba2_max_diag(const BADesc& d, const BAWork2& w, double* sh) {
   if (threadIdx.x < 64) {
     double m = 0;
     for (int g = threadIdx.x; g < w.gP; g += 64) m = fmax(m, w.linpart[2 * g + 1]);
@@ -425,17 +328,13 @@ __device__ __forceinline__ double ba2_lambda_init(const BADesc& d, const BAWork2
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, 64));
-    if (threadIdx.x == 0) *sh = 1e-5 * m;
+    if (threadIdx.x == 0) *sh = m;
   }
   __syncthreads();
   return *sh;
 }
 
 __device__ __forceinline__ Cam ba_cam(const BADesc& d) { return Cam{d.fx, d.fy, d.cx, d.cy, d.bf}; }
-
-// thHuberMono = sqrt(5.991) stored as a float (Optimizer.cc:3457-3458)
-__device__ __forceinline__ double huber_mono() { return (double)(float)sqrt(5.991); }
-__device__ __forceinline__ double huber_stereo() { return (double)(float)sqrt(7.815); }
 
 __global__ __launch_bounds__(kMkThreads) void k_ba2_init(BADesc d, BAWork2 w) {
   const int gt = blockIdx.x * kMkThreads + threadIdx.x, gs = gridDim.x * kMkThreads;
@@ -467,7 +366,6 @@ __global__ __launch_bounds__(kMkThreads) void k_ba2_init(BADesc d, BAWork2 w) {
       memset(&s, 0, sizeof(s));
       s.need_lin = 1;
       s.lam_init = 1;
-      s.ni = 2;
       s.done = d.n_edge == 0 ? 1 : 0;
     }
   }
@@ -745,7 +643,8 @@ __global__ __launch_bounds__(kPtThreads) void k_ba2_p1(BADesc d, BAWork2 w) {
   const BAState* st = w.st;
   if (st->done) return;
   __shared__ double s_lam;
-  const double lambda = st->lam_init ? ba2_lambda_init(d, w, &s_lam) : st->lambda;
+  const double lambda =
+      st->lam_init ? LMStep::lambda_init(ba2_max_diag(d, w, &s_lam)) : st->lm.lam;
   const bool heavy_wg = (int)blockIdx.x >= w.gPp;
   const int lane = threadIdx.x & 63;
   int j = blockIdx.x * kPtThreads + threadIdx.x;
@@ -857,7 +756,8 @@ __global__ __launch_bounds__(kMkSolveThreads) void k_ba2_p3(BADesc d, BAWork2 w)
   const bool lin_ran = need_lin && !stp->spec_ok;
   const int cb = stp->cb;
   __shared__ double s_lam;
-  const double lambda = lam_init ? ba2_lambda_init(d, w, &s_lam) : stp->lambda;
+  const double maxdiag = lam_init ? ba2_max_diag(d, w, &s_lam) : 0.0;
+  const double lambda = lam_init ? LMStep::lambda_init(maxdiag) : stp->lm.lam;
   double* S = n6 <= kLdsRows ? s_S : w.S;
   double* bs = n6 <= kLdsRows ? s_vec : w.vec;
   double* Dg = bs + n6;
@@ -1098,14 +998,12 @@ __global__ __launch_bounds__(kMkSolveThreads) void k_ba2_p3(BADesc d, BAWork2 w)
   if (tid == 0) {
     const double sp = s_vec2[0];
     BAState& s = *stp;
-    if (lin_ran) s.currentChi = s_vec2[1];
-    if (need_lin) s.iniChi = s.currentChi;  // the iteration's start (after an accepted trial: its chi2)
+    if (lin_ran) s.lm.cur = s_vec2[1];
     if (lam_init) {
       s.lam_init = 0;
-      s.ni = 2;
-      s.nBad = 0;
+      s.lm.begin_round(s.lm.cur, maxdiag);  // lm.lam is `lambda` above
     }
-    s.lambda = lambda;
+    if (need_lin) s.lm.begin_iteration();  // after an accepted trial cur is that trial's chi2
     pt[5] = wall_clock64();
     for (int q = 0; q < 5; q++) s.prof[q] += pt[q + 1] - pt[q];
     s.ok2 = ok2 ? 1 : 0;
@@ -1140,48 +1038,22 @@ __device__ void ba2_decide(const BADesc& d, const BAWork2& w) {
   __syncthreads();
   if (tid == 0) {
     BAState& s = *stp;
-    const double tc = s_sum[0], sc = s_sum[1];
-    double tempChi = tc;
-    const double lastTrialChi = tempChi;
-    if (!s.ok2) tempChi = DBL_MAX;
-    double scale = s.scale_p + sc;
-    double rho = s.currentChi - tempChi;
-    scale += 1e-3;
-    rho /= scale;
-    if (rho > 0 && isfinite(tempChi)) {
-      double alpha = 1. - pow((2 * rho - 1), 3);
-      alpha = fmin(alpha, 2. / 3.);
-      s.lambda *= fmax(1. / 3., alpha);
-      s.ni = 2;
-      s.currentChi = tempChi;
+    const double lastTrialChi = s_sum[0], sc = s_sum[1];
+    if (s.lm.trial<LMCube::kPow>(lastTrialChi, s.ok2 != 0, s.scale_p + sc)) {
       s.cb = 1 - s.cb;  // the trial (and its linearisation, with SPEC) becomes the current estimate
       s.spec_ok = w.spec;
     } else {
-      s.lambda *= s.ni;
-      s.ni *= 2;
       s.spec_ok = 0;
     }
-    s.qmax++;
     s.trials[s.round]++;
     int round_end = 0;
-    if (rho < 0 && s.qmax < 10) {
+    if (s.lm.another_trial()) {
       s.need_lin = 0;  // another trial of this iteration
     } else {
-      bool ok = true;
-      if (s.qmax == 10 || rho == 0) ok = false;
-      if (ok) {
-        if ((s.iniChi - s.currentChi) * 1e3 < s.iniChi)
-          s.nBad++;
-        else
-          s.nBad = 0;
-        if (s.nBad >= 3) ok = false;
-      }
-      if (s.chk < lastTrialChi && s.iter > 0) ok = false;
-      s.chk = lastTrialChi;
+      const bool ok = s.lm.end_iteration(s.iter, lastTrialChi);
       s.it_done[s.round] = s.iter + 1;
       s.iter++;
-      s.qmax = 0;
-      s.need_lin = 1;
+      s.need_lin = 1;  // k_ba2_p3 begins the next iteration
       if (!ok || s.iter == (s.round == 0 ? 5 : 10)) round_end = 1;
     }
     if (round_end && s.round == 1) {
@@ -1231,13 +1103,8 @@ __device__ void ba2_decide(const BADesc& d, const BAWork2& w) {
     s.round = 1;
     s.spec_ok = 0;
     s.iter = 0;
-    s.qmax = 0;
     s.need_lin = 1;
-    s.lam_init = 1;
-    s.lambda = 0;
-    s.ni = 2;
-    s.chk = 0;
-    s.nBad = 0;
+    s.lam_init = 1;  // k_ba2_p3 begins the round (lm.begin_round)
     s.nact = (int)t;
     if (t == 0) s.done = 1;
   }
@@ -1257,7 +1124,7 @@ __device__ __forceinline__ void ba2_trial_point(const BADesc& d, const BAWork2& 
   const BAState* st = w.st;
   const int cb = st->cb, nb = 1 - cb;
   const bool ok2 = st->ok2 != 0, robust = st->round == 0;
-  const double lambda = st->lambda;
+  const double lambda = st->lm.lam;
   const size_t n6 = 6 * (size_t)d.n_opt;
   const DSE3* tri = w.pose + (size_t)nb * d.n_kf;
   const double* Xc = w.X + (size_t)cb * 3 * d.n_pt;

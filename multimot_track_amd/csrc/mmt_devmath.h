@@ -529,6 +529,19 @@ __device__ inline double block_sum_regs64(double (&v)[64], double* part, int nw,
   return t;
 }
 
+// LDS written by some lanes of a wave is visible to all of its lanes afterwards (no workgroup
+// barrier: the data is the wave's own)
+__device__ __forceinline__ void wave_sync_lds() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Huber deltas of the map-point edges (D1, local BA): thHuberMono = sqrt(5.991) and thHuberStereo =
+// sqrt(7.815) stored as floats (Optimizer.cc:3457-3458), then setDelta(double)
+__device__ __forceinline__ double huber_mono() { return (double)(float)sqrt(5.991); }
+__device__ __forceinline__ double huber_stereo() { return (double)(float)sqrt(7.815); }
+
 // wave sum of a double, wave-uniform result: quad swaps (xor 1, xor 2), half-row and row mirrors
 // give every lane its 16-lane row sum, then the four row sums are added from lanes 0/16/32/48 in
 // a fixed order.  Inactive lanes must hold 0.

@@ -34,6 +34,7 @@
 
 #include "mmt_devmath.h"
 #include "mmt_internal.h"
+#include "mmt_lmstep.h"
 #include "mmt_track.h"
 
 namespace mmt {
@@ -1003,7 +1004,10 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
         }
       }
       MMT_LMPROF(2);
-      // ---- g2o LM step acceptance and termination (every thread, same values)
+      // ---- g2o LM step acceptance and termination (every thread, same values).  The policy of
+      // mmt_lmstep.h, written out: calling LMStep here changed the register allocation of this
+      // kernel (it sits at the 256-VGPR ceiling) and cost 0.5-0.9 % of the bench (DESIGN.md
+      // section 4).  Keep the two in step.
       const double tempChi = ok2 ? lastTrialChi : DBL_MAX;
 #pragma unroll
       for (int a = 0; a < 6; a++) scale += xb[a] * (lam * xb[a] + lane_value(vc, 23 + a));
@@ -1289,7 +1293,7 @@ namespace {
 
 constexpr int kPoSums = 28;  // [0] robust chi2, [1..21] lower triangle of H, [22..27] b
 
-struct PoEdgeR {  // constant inputs in registers; the last computed error lives in LDS
+struct PoEdgeR {  // an edge's constant inputs and flags; its last computed error is kept beside it
   float X[3], obs[3], s;
   int flags;  // bit 0 stereo, bit 1 outlier (level 1), bit 2 robust kernel
 };
@@ -1299,8 +1303,6 @@ struct PoSmem {
   double tile[4 * 64 * 33];
   double red[16 * 32];
   double H[2][32];  // current / trial sums
-  double e[3][kPoseOptMaxEdges];
-  int flags[kPoseOptMaxEdges];
 };
 
 __device__ __forceinline__ void po_err(const PoEdgeR& E, const DSE3& T, const PoseOptDesc& D,
@@ -1326,8 +1328,8 @@ __device__ __forceinline__ double po_chi2(const PoEdgeR& E, const double e[3]) {
                                : E.s * (e[0] * e[0] + e[1] * e[1]);
 }
 
-// errors at T for an active edge (stored to LDS), robust chi2 and the rho'-weighted
-// J^T Omega J / b terms
+// errors at T for an active edge (stored to eo), robust chi2 and the rho'-weighted
+// J^T Omega J / b terms.  Not to be merged with po_linearise_row: this one rounds without FMA.
 __device__ __forceinline__ void po_linearise(const PoEdgeR& E, const DSE3& T, const PoseOptDesc& D,
                                              double dM, double dS, double* eo, int stride,
                                              double* v) {
@@ -1397,18 +1399,16 @@ __device__ __forceinline__ PoEdgeR po_load(const PoseOptDesc& D, const int* flag
   return E;
 }
 
-// Edges are re-read from global memory (L2-resident, a few KB) on every pass and their flags and
-// last errors live in LDS: no per-thread edge arrays, so the kernel stays clear of spills.
-// GLOBAL: more edges than the LDS arrays hold (kPoseOptMaxEdges): the per-edge errors and flags
-// live in the caller's scratch (D.e_scratch: 3 x N doubles, D.f_scratch: N ints) instead.
-template <bool GLOBAL>
+// The solve for more than kPoseOptMaxEdges edges (the register kernels below take the others).
+// Edges are re-read from global memory on every pass, and their flags and last errors live in the
+// caller's scratch (D.e_scratch: 3 x N doubles, D.f_scratch: N ints): no per-thread edge arrays,
+// so the kernel stays clear of spills.
 __device__ void pose_opt_body(const PoseOptDesc& D, int N, PoSmem& sm) {
   const int tid = threadIdx.x, nt = blockDim.x, nw = nt >> 6;
-  // const float deltaMono = sqrt(5.991): double sqrt rounded to float, then setDelta(double)
-  const double dM = (double)(float)sqrt(5.991), dS = (double)(float)sqrt(7.815);
-  int* flags = GLOBAL ? D.f_scratch : sm.flags;
-  double* const E = GLOBAL ? D.e_scratch : &sm.e[0][0];
-  const int ES = GLOBAL ? N : kPoseOptMaxEdges;  // row stride of the three error rows
+  const double dM = huber_mono(), dS = huber_stereo();
+  int* flags = D.f_scratch;
+  double* const E = D.e_scratch;
+  const int ES = N;  // row stride of the three error rows
   for (int i = tid; i < N; i += nt) {
     flags[i] = (D.obs[3 * i + 2] < 0 ? 0 : kPoStereo) | kPoRobust;
     E[i] = E[ES + i] = E[2 * ES + i] = 0;
@@ -1431,22 +1431,21 @@ __device__ void pose_opt_body(const PoseOptDesc& D, int N, PoSmem& sm) {
     P = P0;
     int hs = 0;
     pass(P, sm.H[0]);  // computeActiveErrors + buildSystem at the round's start
-    double cur = sm.H[0][0], lam, ni = 2, chk = 0;
+    LMStep lm;
     {
       double md = 0;
 #pragma unroll
       for (int a = 0; a < 6; a++) md = fmax(md, fabs(sm.H[0][1 + a * (a + 3) / 2]));
-      lam = 1e-5 * md;
+      lm.begin_round(sm.H[0][0], md);
     }
-    int nRaul = 0;
     double xb[6] = {0, 0, 0, 0, 0, 0};
     for (int iter = 0; iter < 10; iter++) {
-      const double ini = cur;
-      int qmax = 0;
+      lm.begin_iteration();
       bool bad = false;
       for (;;) {
         // ---- solve (H + lambda I) x = b (every thread, identical inputs)
         const double* Hc = sm.H[hs];
+        const double lam = lm.lam;
         double A[21], bs[6];
 #pragma unroll
         for (int q = 0; q < 21; q++) A[q] = Hc[1 + q];
@@ -1462,41 +1461,15 @@ __device__ void pose_opt_body(const PoseOptDesc& D, int N, PoSmem& sm) {
         pass(PN, sm.H[hs ^ 1]);  // trial errors, robust chi2, speculative linearisation
         const double* Ht = sm.H[hs ^ 1];
         const double lastTrialChi = Ht[0];
-        const double tempChi = ok2 ? Ht[0] : DBL_MAX;
         double scale = 0;
 #pragma unroll
         for (int a = 0; a < 6; a++) scale += xb[a] * (lam * xb[a] + Hc[22 + a]);
-        scale += 1e-3;
-        const double rho = (cur - tempChi) / scale;
-        const bool accept = rho > 0 && isfinite(tempChi);
-        if (accept) {
-          const double t = 2 * rho - 1;
-          double alpha = 1. - t * t * t;
-          alpha = fmin(alpha, 2. / 3.);
-          lam = lam * fmax(1. / 3., alpha);
-          ni = 2;
-          cur = tempChi;
+        if (lm.trial<LMCube::kMul>(lastTrialChi, ok2, scale)) {
           P = PN;
           hs ^= 1;
-        } else {
-          lam = lam * ni;
-          ni = ni * 2;
         }
-        qmax++;
-        const bool again = (rho < 0 && qmax < 10);
-        if (!again) {
-          bool ok = true;
-          if (qmax == 10 || rho == 0) ok = false;
-          if (ok) {
-            if ((ini - cur) * 1e3 < ini)
-              nRaul++;
-            else
-              nRaul = 0;
-            if (nRaul >= 3) ok = false;
-          }
-          if (chk < lastTrialChi && iter > 0) ok = false;
-          chk = lastTrialChi;
-          bad = !ok;
+        if (!lm.another_trial()) {
+          bad = !lm.end_iteration(iter, lastTrialChi);
           break;
         }
       }
@@ -1551,7 +1524,8 @@ constexpr int kPoStride = 29;  // odd row stride of the reduction tile (28 sums)
 
 // po_linearise for the register path: the edge's contribution goes straight into the thread's
 // row of the reduction tile (stored by its first edge, FIRST, accumulated by the others; an
-// outlier edge contributes zeros), so the 28 sums never occupy registers.
+// outlier edge contributes zeros), so the 28 sums never occupy registers.  Not to be merged with
+// po_linearise: J and the sums here contract to FMA (fp contract(fast)) and round differently.
 template <bool FIRST>
 __device__ __forceinline__ void po_linearise_row(const PoEdgeR& E, const DSE3& T,
                                                  const PoseOptDesc& D, double dM, double dS,
@@ -1642,7 +1616,7 @@ template <int IT>
 __device__ void pose_opt_light(const PoseOptDesc& D, int N, PoSmemL& sm) {
   const int tid = threadIdx.x, nw = kPoThreads >> 6;
   const int lane = tid & 63, wave = tid >> 6;
-  const double dM = (double)(float)sqrt(5.991), dS = (double)(float)sqrt(7.815);
+  const double dM = huber_mono(), dS = huber_stereo();
   PoEdgeR Ed[IT];
   double er[IT][3];
 #pragma unroll
@@ -1682,9 +1656,7 @@ __device__ void pose_opt_light(const PoseOptDesc& D, int N, PoSmemL& sm) {
     for (int q = 1; q < IT; q++) po_linearise_row<false>(Ed[q], T, D, dM, dS, er[q], row);
     PL_T(1);
     const double* t = sm.tile + (size_t)wave * 64 * kPoStride;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync_lds();
     double* part = sm.part[npass & 1];
     if (lane < kPoSums) {
       double acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1706,9 +1678,7 @@ __device__ void pose_opt_light(const PoseOptDesc& D, int N, PoSmemL& sm) {
       for (int w = 0; w < nw; w++) sum += part[w * 32 + lane];
       sm.Hw[wave][buf][lane] = sum;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_sync_lds();
     PL_T(2);
     npass++;
   };
@@ -1820,6 +1790,7 @@ __device__ void pose_opt_light(const PoseOptDesc& D, int N, PoSmemL& sm) {
           kc++;
         }
         const double lastTrialChi = light(PN);
+        // the policy of mmt_lmstep.h, written out as in flow_lm_body and for the same reason
         const double tempChi = ok2 ? lastTrialChi : DBL_MAX;
         double scale = 0;
 #pragma unroll
@@ -1913,18 +1884,16 @@ __device__ __forceinline__ bool pose_opt_trivial(const PoseOptDesc& D, int N) {
   return true;
 }
 
-// n_lo: counts at or below it belong to another launch (-1: every count)
-__global__ __launch_bounds__(256) void k_pose_opt(const PoseOptDesc* __restrict__ descs,
-                                                  int n_lo) {
+// The register kernels (k_pose_opt_l) take the solves of up to 4 * kPoThreads edges; the callers
+// allocate the scratch of this one only above kPoseOptMaxEdges, so the two rules must agree.
+static_assert(4 * kPoThreads == kPoseOptMaxEdges, "launch rule and scratch rule");
+
+__global__ __launch_bounds__(256) void k_pose_opt(const PoseOptDesc* __restrict__ descs) {
   __shared__ PoSmem sm;
   const PoseOptDesc& D = descs[blockIdx.x];
   const int N = D.n;
-  if (N <= n_lo) return;
-  if (pose_opt_trivial(D, N)) return;
-  if (N <= kPoseOptMaxEdges)
-    pose_opt_body<false>(D, N, sm);
-  else
-    pose_opt_body<true>(D, N, sm);
+  if (N <= kPoseOptMaxEdges) return;  // another launch's (and no scratch to work in)
+  pose_opt_body(D, N, sm);
 }
 
 template <int IT>
@@ -1944,8 +1913,8 @@ void launch_pose_opt(const PoseOptDesc* d_descs, int nsolves, int n_max, hipStre
   // The edge count is known on the device only: every variant whose range meets [0, n_max] is
   // launched and the ones outside the solve's count return at once (n_max is a bound).  Light
   // trial passes + lambda candidates, two edges per thread up to 2 * kPoThreads, four up to
-  // 4 * kPoThreads, the LDS kernel beyond.  One kernel holding several variants spills (580 B per
-  // lane), so each is a launch of its own.  The variants for the larger counts go first: a
+  // 4 * kPoThreads, the scratch kernel beyond.  One kernel holding several variants spills (580 B
+  // per lane), so each is a launch of its own.  The variants for the larger counts go first: a
   // 512-thread workgroup with 132 KB of LDS that queued behind the object path's RANSAC grids
   // waited for them to retire (the motion-model solve's no-op k_pose_opt_l<4> took 5-100 µs,
   // median 64, after its k_pose_opt_l<2>); ahead of it, it is placed before those grids.
@@ -1953,10 +1922,9 @@ void launch_pose_opt(const PoseOptDesc* d_descs, int nsolves, int n_max, hipStre
     hipLaunchKernelGGL(k_pose_opt_l<4>, dim3(nsolves), dim3(kPoThreads), 0, st, d_descs,
                        2 * kPoThreads);
   if (n_max > 4 * kPoThreads)
-    hipLaunchKernelGGL(k_pose_opt, dim3(nsolves), dim3(256), 0, st, d_descs, 4 * kPoThreads);
+    hipLaunchKernelGGL(k_pose_opt, dim3(nsolves), dim3(256), 0, st, d_descs);
   hipLaunchKernelGGL(k_pose_opt_l<2>, dim3(nsolves), dim3(kPoThreads), 0, st, d_descs, -1);
   MMT_HIP(hipGetLastError());
 }
-
 
 }  // namespace mmt

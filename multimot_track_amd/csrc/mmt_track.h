@@ -140,7 +140,7 @@ struct PoseOptDesc {
   double* e_scratch;
   int* f_scratch;
 };
-constexpr int kPoseOptMaxEdges = 2048;  // edges whose state fits the kernel's LDS
+constexpr int kPoseOptMaxEdges = 2048;  // edges the register kernels hold; above, the scratch
 void launch_pose_opt(const PoseOptDesc* d_descs, int nsolves, int n_max, hipStream_t st);
 
 }  // namespace mmt

@@ -237,12 +237,11 @@ static int optimize(const BAProblem& P, const Cam& cam, std::vector<BAEdge>& E, 
   std::vector<double> Hpp(36 * (size_t)nK), bp(6 * (size_t)nK), Hll(9 * (size_t)nP),
       bl(3 * (size_t)nP);
   std::vector<double> xbuf(n6 + 3 * (size_t)nP, 0.0);  // g2o's persistent _x (poses, then points)
-  double lambda = 0, ni = 2, chk = 0;
-  int nBad = 0, it_done = 0;
+  LMPolicy lm;  // oracle_solve.h
+  int it_done = 0;
   for (int iter = 0; iter < iters; iter++) {
     compute_errors();
-    double currentChi = robust_chi2();
-    const double iniChi = currentChi;
+    lm.begin_iteration(robust_chi2());
     // buildSystem
     std::fill(Hpp.begin(), Hpp.end(), 0.0);
     std::fill(bp.begin(), bp.end(), 0.0);
@@ -298,14 +297,12 @@ static int optimize(const BAProblem& P, const Cam& cam, std::vector<BAEdge>& E, 
         for (int a = 0; a < 6; a++) maxd = std::max(maxd, std::fabs(Hpp[36 * (size_t)k + 7 * a]));
       for (int j : pList)
         for (int a = 0; a < 3; a++) maxd = std::max(maxd, std::fabs(Hll[9 * (size_t)j + 4 * a]));
-      lambda = 1e-5 * maxd;
-      ni = 2;
-      nBad = 0;
+      lm.init_lambda(maxd);
     }
-    double rho = 0, lastTrialChi = 0;
-    int qmax = 0;
+    double lastTrialChi = 0;
     do {
       const BAState backup = S;
+      const double lambda = lm.lambda;
       // Schur complement over the points (block_solver.hpp:406-489)
       std::vector<double> Sm((size_t)n6 * n6, 0.0), coef(n6, 0.0);
       for (int a = 0; a < nk; a++) {
@@ -378,10 +375,7 @@ static int optimize(const BAProblem& P, const Cam& cam, std::vector<BAEdge>& E, 
       for (int j : pList)
         for (int a = 0; a < 3; a++) S.X[3 * (size_t)j + a] += xbuf[n6 + 3 * (size_t)j + a];
       compute_errors();
-      double tempChi = robust_chi2();
-      lastTrialChi = tempChi;
-      if (!ok2) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
+      lastTrialChi = robust_chi2();
       double scale = 0;
       for (int a = 0; a < nk; a++)
         for (int r = 0; r < 6; r++)
@@ -390,33 +384,10 @@ static int optimize(const BAProblem& P, const Cam& cam, std::vector<BAEdge>& E, 
         for (int a = 0; a < 3; a++)
           scale += xbuf[n6 + 3 * (size_t)j + a] *
                    (lambda * xbuf[n6 + 3 * (size_t)j + a] + bl[3 * (size_t)j + a]);
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - std::pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        lambda *= std::max(1. / 3., alpha);
-        ni = 2;
-        currentChi = tempChi;
-      } else {
-        lambda *= ni;
-        ni *= 2;
-        S = backup;
-      }
-      qmax++;
+      if (!lm.trial(lastTrialChi, ok2, scale)) S = backup;
       if (trials) (*trials)++;
-    } while (rho < 0 && qmax < 10);
-    bool ok = true;
-    if (qmax == 10 || rho == 0) ok = false;
-    if (ok) {
-      if ((iniChi - currentChi) * 1e3 < iniChi)
-        nBad++;
-      else
-        nBad = 0;
-      if (nBad >= 3) ok = false;
-    }
-    if (chk < lastTrialChi && iter > 0) ok = false;  // sparse_optimizer.cpp:393-396
-    chk = lastTrialChi;
+    } while (lm.another_trial());
+    const bool ok = lm.end_iteration(iter, lastTrialChi);
     it_done = iter + 1;
     if (!ok) break;
   }

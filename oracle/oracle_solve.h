@@ -1,11 +1,74 @@
 // oracle/oracle_solve.h -- TEST INFRASTRUCTURE ONLY (see orb_ref.cpp header).
 #pragma once
+#include <algorithm>
+#include <cfloat>
+#include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "oracle_common.h"
 
 namespace oracle {
+
+// g2o's Levenberg-Marquardt step policy as the three solves below run it
+// (OptimizationAlgorithmLevenberg::solve and ORB-SLAM2's SparseOptimizer::optimize): the checker's
+// own restatement, on purpose not shared with the product's.  A solve keeps one LMPolicy per
+// optimize() call; every iteration re-evaluates chi2 and calls begin_iteration, iteration 0 also
+// init_lambda.
+struct LMPolicy {
+  double lambda = 0, ni = 2, chk = 0;
+  double currentChi = 0, iniChi = 0, rho = 0;
+  int qmax = 0, nBad = 0;
+
+  void begin_iteration(double chi) {
+    currentChi = iniChi = chi;
+    rho = 0;
+    qmax = 0;
+  }
+  void init_lambda(double maxDiagonal) {  // computeLambdaInit: tau * max |hessian diagonal|
+    lambda = 1e-5 * maxDiagonal;
+    ni = 2;
+    nBad = 0;
+  }
+  // lastTrialChi: the robust chi2 at the trial state; ok2: the linear solve succeeded; scale:
+  // x^T (lambda x + b).  False: the caller restores its backup.
+  bool trial(double lastTrialChi, bool ok2, double scale) {
+    double tempChi = lastTrialChi;
+    if (!ok2) tempChi = DBL_MAX;
+    rho = currentChi - tempChi;
+    scale += 1e-3;
+    rho /= scale;
+    qmax++;
+    if (rho > 0 && std::isfinite(tempChi)) {
+      double alpha = 1. - std::pow((2 * rho - 1), 3);
+      alpha = std::min(alpha, 2. / 3.);
+      lambda *= std::max(1. / 3., alpha);
+      ni = 2;
+      currentChi = tempChi;
+      return true;
+    }
+    lambda *= ni;
+    ni *= 2;
+    return false;
+  }
+  bool another_trial() const { return rho < 0 && qmax < 10; }
+  // after the iteration's last trial; false stops optimize()
+  bool end_iteration(int iter, double lastTrialChi) {
+    bool ok = true;
+    if (qmax == 10 || rho == 0) ok = false;  // Terminate
+    if (ok) {  // Raul's stop
+      if ((iniChi - currentChi) * 1e3 < iniChi)
+        nBad++;
+      else
+        nBad = 0;
+      if (nBad >= 3) ok = false;
+    }
+    // sparse_optimizer.cpp:393-396 (modified g2o): stop when the robust chi2 increased
+    if (chk < lastTrialChi && iter > 0) ok = false;
+    chk = lastTrialChi;
+    return ok;
+  }
+};
 
 // One flow-refined pose solve (Optimizer::PoseOptimizationFlow2Cam / PoseOptimizationFlow2).
 struct FlowProblem {

@@ -226,18 +226,15 @@ int flow_pose_solve(const FlowProblem& P, float pose_out[16], FlowSolveStats* st
     return chi;
   };
 
-  double lambda = 0, ni = 2;
-  int nBad = 0;
+  LMPolicy lm;  // oracle_solve.h
   double xbuf[6] = {0, 0, 0, 0, 0, 0};  // g2o's persistent _x (stale on a failed solve)
   std::vector<double> xl(2 * N, 0.0);
   std::vector<double> Bm(12 * N), h(N), bl(2 * N);
-  double chi2_check = 0;
   int it_done = 0;
   for (int iter = 0; iter < P.max_iters; iter++) {
     // ---- OptimizationAlgorithmLevenberg::solve
     compute_errors(pose, f);
-    double currentChi = robust_chi2();
-    const double iniChi = currentChi;
+    lm.begin_iteration(robust_chi2());
     // buildSystem at the current state
     double Hpp[6][6] = {{0}}, bp[6] = {0};
     bool clean = true;  // no Huber-active edge at this linearisation (test statistic)
@@ -268,14 +265,12 @@ int flow_pose_solve(const FlowProblem& P, float pose_out[16], FlowSolveStats* st
       double maxd = 0;
       for (int a = 0; a < 6; a++) maxd = std::max(maxd, std::fabs(Hpp[a][a]));
       for (int i = 0; i < N; i++) maxd = std::max(maxd, std::fabs(h[i]));
-      lambda = 1e-5 * maxd;
-      ni = 2;
-      nBad = 0;
+      lm.init_lambda(maxd);
     }
-    double rho = 0;
-    int qmax = 0, run = 0;
+    int run = 0;
     double lastTrialChi = 0;
     do {
+      const double lambda = lm.lambda;
       const SE3 pose_b = pose;
       fb = f;
       // ---- BlockSolver::solve with the lambda-augmented diagonals
@@ -318,25 +313,11 @@ int flow_pose_solve(const FlowProblem& P, float pose_out[16], FlowSolveStats* st
       pose = se3_mul(se3_exp(xbuf), pose);
       for (int i = 0; i < 2 * N; i++) f[i] += xl[i];
       compute_errors(pose, f);
-      double tempChi = robust_chi2();
-      lastTrialChi = tempChi;
-      if (!ok2) tempChi = DBL_MAX;
-      rho = currentChi - tempChi;
+      lastTrialChi = robust_chi2();
       double scale = 0;
       for (int a = 0; a < 6; a++) scale += xbuf[a] * (lambda * xbuf[a] + bp[a]);
       for (int i = 0; i < 2 * N; i++) scale += xl[i] * (lambda * xl[i] + bl[i]);
-      scale += 1e-3;
-      rho /= scale;
-      if (rho > 0 && std::isfinite(tempChi)) {
-        double alpha = 1. - std::pow((2 * rho - 1), 3);
-        alpha = std::min(alpha, 2. / 3.);
-        const double sf = std::max(1. / 3., alpha);
-        lambda *= sf;
-        ni = 2;
-        currentChi = tempChi;
-      } else {
-        lambda *= ni;
-        ni *= 2;
+      if (!lm.trial(lastTrialChi, ok2, scale)) {
         pose = pose_b;
         f = fb;
         if (st) {
@@ -345,22 +326,9 @@ int flow_pose_solve(const FlowProblem& P, float pose_out[16], FlowSolveStats* st
           st->max_reject_run = std::max(st->max_reject_run, ++run);
         }
       }
-      qmax++;
-    } while (rho < 0 && qmax < 10);
-    bool ok = true;
-    if (qmax == 10 || rho == 0) ok = false;  // Terminate
-    if (ok) {
-      if ((iniChi - currentChi) * 1e3 < iniChi)
-        nBad++;
-      else
-        nBad = 0;
-      if (nBad >= 3) ok = false;
-    }
-    // sparse_optimizer.cpp:393-396 (modified g2o): stop when the robust chi2 increased
-    if (chi2_check < lastTrialChi && iter > 0) ok = false;
-    chi2_check = lastTrialChi;
+    } while (lm.another_trial());
     it_done = iter + 1;
-    if (!ok) break;
+    if (!lm.end_iteration(iter, lastTrialChi)) break;
   }
   se3_to_float(pose, pose_out);
   // outlier count from the edges' last computed errors (Optimizer.cc:536-566)
@@ -459,14 +427,12 @@ int pose_optimization(const PoseOptProblem& P, float pose_out[16], uint8_t* outl
   int nBad = 0;
   for (int it = 0; it < 4; it++) {
     pose = se3_from_float(P.Tcw);  // vSE3->setEstimate(toSE3Quat(pFrame->mTcw))
-    double lambda = 0, ni = 2, chk = 0;
-    int nRaul = 0;
+    LMPolicy lm;
     double xbuf[6] = {0, 0, 0, 0, 0, 0};
     for (int iter = 0; iter < 10; iter++) {
       for (int i = 0; i < N; i++)
         if (!E[i].outlier) po_error(E[i], pose, fx, fy, cx, cy, bf, E[i].e);
-      double currentChi = robust_chi2();
-      const double iniChi = currentChi;
+      lm.begin_iteration(robust_chi2());
       double H[6][6] = {{0}}, b[6] = {0};
       for (int i = 0; i < N; i++) {
         if (E[i].outlier) continue;
@@ -508,17 +474,15 @@ int pose_optimization(const PoseOptProblem& P, float pose_out[16], uint8_t* outl
       if (iter == 0) {
         double maxd = 0;
         for (int a = 0; a < 6; a++) maxd = std::max(maxd, std::fabs(H[a][a]));
-        lambda = 1e-5 * maxd;
-        ni = 2;
-        nRaul = 0;
+        lm.init_lambda(maxd);
       }
       // g2o accumulates b -= rho' J^T Omega e and solves (H + lambda I) dx = b
       double rhs[6];
       for (int a = 0; a < 6; a++) rhs[a] = b[a];
-      double rho = 0, lastTrialChi = 0;
-      int qmax = 0;
+      double lastTrialChi = 0;
       do {
         const SE3 pose_b = pose;
+        const double lambda = lm.lambda;
         double Hs[6][6];
         for (int a = 0; a < 6; a++)
           for (int c = 0; c < 6; c++) Hs[a][c] = H[a][c] + (a == c ? lambda : 0.0);
@@ -528,39 +492,12 @@ int pose_optimization(const PoseOptProblem& P, float pose_out[16], uint8_t* outl
         pose = se3_mul(se3_exp(xbuf), pose);
         for (int i = 0; i < N; i++)
           if (!E[i].outlier) po_error(E[i], pose, fx, fy, cx, cy, bf, E[i].e);
-        double tempChi = robust_chi2();
-        lastTrialChi = tempChi;
-        if (!ok2) tempChi = DBL_MAX;
-        rho = currentChi - tempChi;
+        lastTrialChi = robust_chi2();
         double scale = 0;
         for (int a = 0; a < 6; a++) scale += xbuf[a] * (lambda * xbuf[a] + rhs[a]);
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-          double alpha = 1. - std::pow((2 * rho - 1), 3);
-          alpha = std::min(alpha, 2. / 3.);
-          lambda *= std::max(1. / 3., alpha);
-          ni = 2;
-          currentChi = tempChi;
-        } else {
-          lambda *= ni;
-          ni *= 2;
-          pose = pose_b;
-        }
-        qmax++;
-      } while (rho < 0 && qmax < 10);
-      bool ok = true;
-      if (qmax == 10 || rho == 0) ok = false;
-      if (ok) {
-        if ((iniChi - currentChi) * 1e3 < iniChi)
-          nRaul++;
-        else
-          nRaul = 0;
-        if (nRaul >= 3) ok = false;
-      }
-      if (chk < lastTrialChi && iter > 0) ok = false;
-      chk = lastTrialChi;
-      if (!ok) break;
+        if (!lm.trial(lastTrialChi, ok2, scale)) pose = pose_b;
+      } while (lm.another_trial());
+      if (!lm.end_iteration(iter, lastTrialChi)) break;
     }
     // re-classification (Optimizer.cc:3266-3322): edges that sat this round out get their error
     // at the optimised pose; the others keep the last computed one

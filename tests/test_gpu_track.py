@@ -296,7 +296,7 @@ def test_track_c5_eight_motions_250_frames_matches_oracle(oracle_mod):
 def test_pose_optimization_matches_oracle(ctx, oracle_mod, seed, n, out, mono):
     """D1 (Optimizer::PoseOptimization): pose within 1e-4, mvbOutlier and the inlier count
     exact, for mixed mono/stereo edges, outliers, the one-round (< 10 edges) case, the 2048
-    edges whose state fits the kernel's LDS and the global-scratch path beyond (C4/C5 frames
+    edges the register kernels hold and the global-scratch path beyond (C4/C5 frames
     carry up to 8000 keys)."""
     from synth_problems import pose_opt_problem
     Xw, obs, s2, init, _ = pose_opt_problem(seed, n, outlier_frac=out, mono_frac=mono)
