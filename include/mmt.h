@@ -51,6 +51,10 @@
  *                          Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1338-1424)
  *   mmt_bow_transform   <- TemplatedVocabulary::transform(feature, word, weight, &node, levelsup)
  *                          TemplatedVocabulary.h:1218-1259 (Frame::ComputeBoW, Frame.cc:778-786)
+ *   mmt_train_vocabulary <- TemplatedVocabulary::create(training_features, k, L, weighting,
+ *                          scoring) TemplatedVocabulary.h:558-616 (HKmeansStep :642-819,
+ *                          initiateClustersKMpp :833-913, setNodeWeights :943-996)
+ *   mmt_save_vocabulary <- TemplatedVocabulary::saveToTextFile TemplatedVocabulary.h:1429-1449
  *   mmt_destroy         <- System::Shutdown / delete
  */
 #ifndef MMT_H
@@ -474,6 +478,42 @@ int mmt_load_vocabulary(mmt_ctx* ctx, const char* path);
  * n x 32) on the GPU: word id, word weight (0: stopped) and the node at level L - levelsup. */
 int mmt_bow_transform(mmt_ctx* ctx, const uint8_t* desc, int n, int levelsup, uint32_t* word,
                       double* weight, uint32_t* node);
+
+/* ---- training a vocabulary ------------------------------------------------------------------------
+ * TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the GPU: hierarchical
+ * k-medians (k-means++ seeding, Lloyd iterations with FORB::meanValue's bit majority) level by
+ * level, then setNodeWeights.  Every decision is an integer, so the tree is bit-identical to a
+ * sequential run of the reference's steps.  Pinned where the reference leaves a choice (DESIGN.md
+ * section 2): the random stream (seed; the reference seeds rand() from the wall clock), an emptied
+ * cluster keeps its centre, max_iters caps the Lloyd iterations of a level. */
+typedef struct mmt_voc_train_params {
+  int k, L;            /* branching factor 2..20, depth 1..10 (the loader's limits; k >= 2)     */
+  int weighting;       /* DBoW2 WeightingType: 0 TF_IDF, 1 TF, 2 IDF, 3 BINARY                  */
+  int scoring;         /* DBoW2 ScoringType: 0 L1_NORM, 1 L2_NORM (what the loader accepts)     */
+  uint64_t seed;       /* replaces SeedRandOnce()'s wall clock                                  */
+  int max_iters;       /* cap on Lloyd iterations per level, 0 -> 1000                          */
+} mmt_voc_train_params;
+typedef struct mmt_voc_train_stats {
+  int32_t n_nodes;          /* nodes of the tree, the root included                             */
+  int32_t n_words;          /* leaves                                                           */
+  int32_t n_kmeans_nodes;   /* nodes with more than k features (k-means ran)                    */
+  int32_t n_capped;         /* nodes whose assignment still changed at max_iters                */
+  int32_t n_empty_clusters; /* clusters left without a feature (childless nodes)                */
+  int32_t iters[10];        /* Lloyd iterations run at tree level 1..L                          */
+} mmt_voc_train_stats;
+/* desc is image_start[n_images] x 32 bytes on the host, image i owning rows [image_start[i],
+ * image_start[i + 1]).  Installs the result as the context's vocabulary, with full-precision
+ * weights, under mmt_load_vocabulary's rule (MMT_ESTATE once the map has a keyframe).  MMT_EINVAL:
+ * no descriptors or images, k or L out of range, a scoring above 1, a decreasing image_start. */
+int mmt_train_vocabulary(mmt_ctx* ctx, const uint8_t* desc, const int32_t* image_start,
+                         int n_images, const mmt_voc_train_params* params,
+                         mmt_voc_train_stats* stats);
+
+/* TemplatedVocabulary::saveToTextFile of the context's vocabulary (trained or loaded): the header
+ * "k L  scoring weighting", one line per node in id order "parent leaf d0 .. d31  weight" with the
+ * weight in six significant digits.  MMT_EINVAL without a vocabulary or when the file cannot be
+ * written. */
+int mmt_save_vocabulary(mmt_ctx* ctx, const char* path);
 
 /* The keyframe's map points as Relocalization's SearchByProjection reads them, in the keyframe's
  * mvpMapPoints order: world position, mfMinDistance / mfMaxDistance, mDescriptor and the angle of

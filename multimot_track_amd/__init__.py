@@ -121,6 +121,17 @@ class MmtBowCounters(ctypes.Structure):
                                                "triangulated", "sft_matches", "kfdb")]
 
 
+class MmtVocTrainParams(ctypes.Structure):
+    _fields_ = [("k", ctypes.c_int), ("L", ctypes.c_int), ("weighting", ctypes.c_int),
+                ("scoring", ctypes.c_int), ("seed", ctypes.c_uint64), ("max_iters", ctypes.c_int)]
+
+
+class MmtVocTrainStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in ("n_nodes", "n_words", "n_kmeans_nodes", "n_capped",
+                                               "n_empty_clusters")] + \
+               [("iters", ctypes.c_int32 * 10)]
+
+
 MAP_DUMP_FIELDS = (("kf_i", np.int64, 4), ("kf_T", np.float32, 16), ("kf_mps_start", np.int32, 1),
                    ("kf_mps", np.int32, 1), ("pt_f", np.float32, 5), ("pt_i", np.int32, 5),
                    ("obs_start", np.int32, 1), ("obs_i", np.int32, 3), ("obs_f", np.float32, 4),
@@ -294,6 +305,9 @@ def lib():
         L.mmt_set_keyframe_culling_ratio.argtypes = [vp, ctypes.c_double]
         L.mmt_load_vocabulary.argtypes = [vp, ctypes.c_char_p]
         L.mmt_bow_transform.argtypes = [vp, vp, i32, i32, vp, vp, vp]
+        L.mmt_train_vocabulary.argtypes = [vp, vp, vp, i32, ctypes.POINTER(MmtVocTrainParams),
+                                           ctypes.POINTER(MmtVocTrainStats)]
+        L.mmt_save_vocabulary.argtypes = [vp, ctypes.c_char_p]
         L.mmt_bow_counters_read.argtypes = [vp, ctypes.POINTER(MmtBowCounters)]
         L.mmt_set_deferred_objects.argtypes = [vp, i32]
         L.mmt_flush_objects.argtypes = [vp, vp, vp, i32, i32, vp]
@@ -706,6 +720,29 @@ class Context:
         """System(voc, ...): DBoW2 text vocabulary; with it the tracker runs the reference's
         TrackReferenceKeyFrame, Relocalization and CreateNewMapPoints (mmt_load_vocabulary)."""
         self._check(lib().mmt_load_vocabulary(self._h, path.encode()))
+
+    def train_vocabulary(self, descs_per_image, k=10, L=6, weighting=0, scoring=0, seed=0,
+                         max_iters=0):
+        """TemplatedVocabulary::create(training_features, k, L, weighting, scoring) on the GPU
+        (mmt_train_vocabulary): descs_per_image is one (n_i, 32) uint8 array per training image.
+        Installs the vocabulary in the context; returns the training statistics."""
+        imgs = [np.ascontiguousarray(d, np.uint8).reshape(-1, 32) for d in descs_per_image]
+        start = np.zeros(len(imgs) + 1, np.int32)
+        if imgs:
+            start[1:] = np.cumsum([len(d) for d in imgs])
+        desc = np.ascontiguousarray(np.concatenate(imgs)) if imgs else np.zeros((0, 32), np.uint8)
+        prm = MmtVocTrainParams(k, L, weighting, scoring, seed, max_iters)
+        st = MmtVocTrainStats()
+        self._check(lib().mmt_train_vocabulary(self._h, _p(desc), _p(start), len(imgs),
+                                               ctypes.byref(prm), ctypes.byref(st)))
+        out = {k_: int(getattr(st, k_)) for k_, _ in MmtVocTrainStats._fields_[:5]}
+        out["iters"] = [int(v) for v in st.iters[:L]]
+        return out
+
+    def save_vocabulary(self, path):
+        """TemplatedVocabulary::saveToTextFile of the context's vocabulary
+        (mmt_save_vocabulary)."""
+        self._check(lib().mmt_save_vocabulary(self._h, path.encode()))
 
     def bow_transform(self, desc, levelsup=4):
         """Per descriptor (word, weight, node at level L - levelsup) on the GPU."""

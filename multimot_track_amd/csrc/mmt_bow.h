@@ -46,6 +46,14 @@ class Vocabulary {
   ~Vocabulary();
   // TemplatedVocabulary::loadFromTextFile; throws ArgError with the reason
   void load_text(const char* path);
+  // TemplatedVocabulary::saveToTextFile (TemplatedVocabulary.h:1429-1449); throws ArgError
+  void save_text(const char* path) const;
+  // the tree create() leaves in memory (mmt_voctrain.hip): parent (parent[0] = -1, a parent before
+  // its children, a node's children in ascending id) and descriptors of all nodes, root included;
+  // every weight 0 until set_word_weights
+  void set_tree(int k, int L, int scoring, int weighting, const std::vector<int>& parent,
+                const std::vector<uint8_t>& desc);
+  void set_word_weights(const std::vector<double>& w);  // n_words(), in word order
   // the tree on the device (once, on the first transform)
   void upload();
   bool empty() const { return words_ == 0; }

@@ -111,6 +111,61 @@ void Vocabulary::load_text(const char* path) {
   }
 }
 
+void Vocabulary::set_tree(int k_, int L_, int scoring_, int weighting_,
+                          const std::vector<int>& parent, const std::vector<uint8_t>& desc) {
+  const size_t nn = parent.size();
+  k = k_;
+  L = L_;
+  scoring = scoring_;
+  weighting = weighting_;
+  desc_ = desc;
+  weight_.assign(nn, 0.0);
+  std::vector<int> nchild(nn, 0);
+  for (size_t n = 1; n < nn; n++) nchild[parent[n]]++;
+  child_start_.assign(nn + 1, 0);
+  for (size_t n = 0; n < nn; n++) child_start_[n + 1] = child_start_[n] + nchild[n];
+  child_.assign(nn > 0 ? nn - 1 : 0, 0);
+  std::vector<int> fill(child_start_.begin(), child_start_.end() - 1);
+  for (size_t n = 1; n < nn; n++) child_[fill[parent[n]]++] = (int)n;
+  word_of_.assign(nn, -1);
+  words_ = 0;
+  for (size_t n = 1; n < nn; n++)
+    if (nchild[n] == 0) word_of_[n] = words_++;
+  if (d_block_) {
+    (void)hipFree(d_block_);
+    d_block_ = nullptr;
+  }
+}
+
+void Vocabulary::set_word_weights(const std::vector<double>& w) {
+  for (size_t n = 0; n < word_of_.size(); n++)
+    if (word_of_[n] >= 0) weight_[n] = w[word_of_[n]];
+  if (d_block_) {
+    (void)hipFree(d_block_);
+    d_block_ = nullptr;
+  }
+}
+
+void Vocabulary::save_text(const char* path) const {
+  std::ofstream f(path);
+  if (!f.is_open()) throw ArgError(std::string("cannot write vocabulary ") + path);
+  const size_t nn = word_of_.size();
+  std::vector<int> parent(nn, -1);
+  for (size_t n = 0; n < nn; n++)
+    for (int c = child_start_[n]; c < child_start_[n + 1]; c++) parent[child_[c]] = (int)n;
+  f << k << " " << L << " " << " " << scoring << " " << weighting << std::endl;
+  std::ostringstream line;
+  for (size_t n = 1; n < nn; n++) {
+    line.str("");
+    line << parent[n] << " " << (word_of_[n] >= 0 ? 1 : 0) << " ";
+    for (int i = 0; i < 32; i++) line << (int)desc_[32 * n + i] << " ";  // FORB::toString
+    line << " " << weight_[n] << "\n";
+    f << line.str();
+  }
+  f.flush();
+  if (!f.good()) throw ArgError(std::string("cannot write vocabulary ") + path);
+}
+
 void Vocabulary::upload() {
   if (d_block_) return;
   const size_t nn = word_of_.size();

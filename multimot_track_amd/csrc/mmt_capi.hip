@@ -15,6 +15,7 @@
 #include "mmt_match.h"
 #include "mmt_pnp.h"
 #include "mmt_track.h"
+#include "mmt_voctrain.h"
 
 using mmt::ArgError;
 using mmt::DeviceError;
@@ -903,6 +904,38 @@ int mmt_load_vocabulary(mmt_ctx* ctx, const char* path) {
     return MMT_ESTATE;
   }
   return rc;
+}
+
+int mmt_train_vocabulary(mmt_ctx* ctx, const uint8_t* desc, const int32_t* image_start,
+                         int n_images, const mmt_voc_train_params* params,
+                         mmt_voc_train_stats* stats) {
+  if (!ctx || !desc || !image_start || n_images <= 0 || !params || !stats) return MMT_EINVAL;
+  bool late = false;
+  const int rc = guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    ensure_tracker(ctx);
+    if (ctx->tracker.map().n_keyframes() > 0 || ctx->tracker.map().state() != 0) {
+      late = true;
+      return;
+    }
+    std::unique_ptr<mmt::Vocabulary> v(new mmt::Vocabulary());
+    mmt::train_vocabulary(desc, image_start, n_images, *params, *v, *stats, ctx->stream);
+    ctx->tracker.set_vocabulary(v.get());
+    ctx->voc = std::move(v);
+  });
+  if (rc == MMT_OK && late) {
+    ctx->err = "mmt_train_vocabulary: train the vocabulary before the first frame";
+    return MMT_ESTATE;
+  }
+  return rc;
+}
+
+int mmt_save_vocabulary(mmt_ctx* ctx, const char* path) {
+  if (!ctx || !path) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (!ctx->voc) throw mmt::ArgError("mmt_save_vocabulary: no vocabulary loaded or trained");
+    ctx->voc->save_text(path);
+  });
 }
 
 int mmt_bow_transform(mmt_ctx* ctx, const uint8_t* desc, int n, int levelsup, uint32_t* word,
