@@ -630,7 +630,8 @@ int mmt_set_deferred_objects(mmt_ctx* ctx, int on);
 int mmt_flush_objects(mmt_ctx* ctx, mmt_frame_result* res, mmt_motion* objs, int objs_cap,
                       int res_cap, int* n);
 
-/* Upper bound on keypoints per frame (sum over levels of quota + 3). */
+/* Upper bound on keypoints per frame: the sum over levels of max(quota, 4 * nIni) + 8 slots, where
+ * DistributeOctTree keeps at most max(quota + 2, 4 * nIni) keys. */
 int mmt_orb_capacity(const mmt_ctx* ctx);
 
 /* ---- Debug and test hooks: not part of the stable interface, no reference counterpart ---- */

@@ -1891,7 +1891,11 @@ void OrbEngine::setup(int w, int h, const OrbTables& t, int max_batch) {
     L.N = t.nPerLevel[l];
     maxN = std::max(maxN, L.N);
     L.out_off = out_off;
-    L.out_cap = L.N + 8;
+    // DistributeOctTree returns at most N + 2 nodes once a pass starts below N (every later pass
+    // is bounded by the `size + 3 * nToExpand > N` test, :673), but the first pass turns the nIni
+    // initial nodes into up to 4 * nIni whatever N is: a wide level with a small quota (1229 x
+    // 221 at 300 features: nIni 7, N 18 on level 7) keeps more than N + 8 keys
+    L.out_cap = std::max(L.N, 4 * L.nIni) + 8;
     out_off += L.out_cap;
     L.scale = t.scale[l];
     L.size = (float)(int)(31 * t.scale[l]);
@@ -1965,7 +1969,8 @@ void OrbEngine::setup(int w, int h, const OrbTables& t, int max_batch) {
   while (node_cap_ < maxN + 16) node_cap_ <<= 1;
   for (auto& L : lv_) {
     while (L.cell_end - L.cell_begin > 4 * node_cap_) node_cap_ <<= 1;  // gather scratch
-    if (L.nIni > node_cap_) throw ArgError("too many initial octree nodes");
+    // the first pass writes up to 4 * nIni nodes before the kernel's capacity guard looks
+    if (4 * L.nIni + 4 > node_cap_) throw ArgError("too many initial octree nodes");
   }
   if (node_cap_ > 2048) throw ArgError("ORB nfeatures too large for the LDS octree (max ~9000)");
   for (int fs : {kFSSmall, kFSMax}) {

@@ -1,5 +1,9 @@
 """GPU parity of the HIP ORB extractor against the CPU oracle (bit-exact: keypoint records and
-descriptors compared as bytes), stage by stage so a failure names the kernel."""
+descriptors compared as bytes).  _check_stages compares the pyramid and the blur (debug buffers 0
+and 1) with the oracle's, so a failure there names k_pyramid/k_resize or k_blur; the FAST and
+octree buffers (2-5), the k_resize chain of batches above 32 frames, the tiling edges and padded
+strides are checked stage by stage in tests/test_gpu_orb_stages.py, against the independent
+restatement tests/orb_ref_py.py."""
 import numpy as np
 import pytest
 
