@@ -55,6 +55,9 @@
  *                          scoring) TemplatedVocabulary.h:558-616 (HKmeansStep :642-819,
  *                          initiateClustersKMpp :833-913, setNodeWeights :943-996)
  *   mmt_save_vocabulary <- TemplatedVocabulary::saveToTextFile TemplatedVocabulary.h:1429-1449
+ *   mmt_stereo_frame    <- System::TrackStereo -> Tracking::GrabImageStereo's stereo Frame
+ *                          constructor Frame.cc:79-159
+ *   mmt_stereo_matches  <- Frame::ComputeStereoMatches Frame.cc:849-1038
  *   mmt_destroy         <- System::Shutdown / delete
  */
 #ifndef MMT_H
@@ -629,6 +632,67 @@ int mmt_reset(mmt_ctx* ctx);
 int mmt_set_deferred_objects(mmt_ctx* ctx, int on);
 int mmt_flush_objects(mmt_ctx* ctx, mmt_frame_result* res, mmt_motion* objs, int objs_cap,
                       int res_cap, int* n);
+
+/* ---- Stereo frames: keypoint depth from a rectified image pair ----------------------------------
+ * Counters of Frame::ComputeStereoMatches (Frame.cc:849-1038), one per rejection stage (no
+ * reference counterpart: they make every stage observable).  n_coarse = n_window_edge +
+ * n_end_shift + n_delta + n_range + n_accepted. */
+typedef struct mmt_stereo_counters {
+  int32_t n_coarse;          /* left keys whose best Hamming distance is below thOrbDist = 75
+                                (Frame.cc:949)                                              */
+  int32_t n_window_edge;     /* skipped by the border test of Frame.cc:972, or because the first
+                                shifted window would start left of column 0 (pinned, below) */
+  int32_t n_end_shift;       /* best shift -5 or +5 (Frame.cc:991)                          */
+  int32_t n_delta;           /* parabola offset outside [-1, 1] (Frame.cc:1001)             */
+  int32_t n_range;           /* disparity outside [0, 200) (Frame.cc:1009; a NaN lands here) */
+  int32_t n_clamped;         /* accepted with a disparity of 0, set to 0.01 (Frame.cc:1011-1015) */
+  int32_t n_accepted;        /* vDistIdx.size()                                             */
+  int32_t n_median_removed;  /* cleared by the median filter (Frame.cc:1027-1037)           */
+  int32_t median;            /* vDistIdx[size / 2].first (-1: no accepted key)              */
+  float th_dist;             /* thDist = 1.5f * 1.4f * median (0: no accepted key)          */
+} mmt_stereo_counters;
+
+/* Frame::ComputeStereoMatches (Frame.cc:849-1038; this fork: minD = 0, maxD = 200 pixels, the
+ * vDescIndex output) on caller-supplied keys.  left / right: 8-bit gray images of the context's
+ * size (host pointers, row stride `stride`); both pyramids are built with the extractor's pyramid
+ * stage (ORBextractor::ComputePyramid, ORBextractor.cc:1111-1136; no FAST), since the 11 x 11
+ * correlation windows are read from the unblurred level of the left key (Frame.cc:960, 977).
+ * kps / desc (n x 32) of both sides as the extractor writes them; n <= 16384 per side.
+ * Outputs (n_left each): uR = mvuRight and depth = mvDepth (-1 without a match), right_idx =
+ * vDescIndex (Frame.cc:943-944: the best right key unless it is key 0, which is never reported;
+ * -1 again when the median filter clears the match); optional best_dist = the coarse search's
+ * bestDist (100 when no candidate is closer, -1 when the key's row lists no right key) and sad =
+ * the window search's bestDist (-1 where it is not reached).  Camera.bf from the configuration.
+ * Pinned where the reference is undefined: without an accepted match nothing is cleared (the
+ * reference reads an empty vector, Frame.cc:1024); a right key closer than 10 level pixels to the
+ * left border (OpenCV would throw in colRange, Frame.cc:977) is skipped like Frame.cc:972.
+ * MMT_EINVAL before any launch: config.max_batch < 2 (the device pyramid is frame-major per batch
+ * slot, and a pair needs two slots), an octave outside the pyramid, a left key whose 11 x 11 window
+ * leaves its level or whose row (int)y leaves the image, a right key whose row range floor(y - r)
+ * .. ceil(y + r) (Frame.cc:873-878) leaves [0, rows). */
+int mmt_stereo_matches(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h,
+                       int stride, int n_left, const mmt_kp* kps_left, const uint8_t* desc_left,
+                       int n_right, const mmt_kp* kps_right, const uint8_t* desc_right, float* uR,
+                       float* depth, int32_t* right_idx, int32_t* best_dist, int32_t* sad,
+                       mmt_stereo_counters* counters);
+
+/* The stereo Frame constructor (Frame.cc:79-159) as System::TrackStereo -> Tracking::
+ * GrabImageStereo reaches it: both gray images extracted as one batch of two (replacing the two
+ * ExtractORB threads of Frame.cc:96-99), vSemLabel[i] = mask(int(y), int(x)) (Frame.cc:116-124;
+ * mask: optional w x h int32, rows packed; sem_label is written only with a mask), mvKeysUn ==
+ * mvKeys (no distortion), then ComputeStereoMatches against the two pyramids of the batch in
+ * place.  kps / desc: the left keys, level-major and bit-identical to mmt_orb_extract(left);
+ * kps_right / desc_right: the right keys.  *n / *n_right receive the counts; MMT_ENOSPC, as
+ * mmt_orb_extract, when cap (the slots of kps, desc, uR, depth, right_idx, sem_label) or cap_right
+ * is short of its count (known once the extraction has run; nothing is matched or copied then).
+ * Without a left key (the early return of Frame.cc:103) the left outputs are empty and *n_right is
+ * still reported.  MMT_EINVAL before any launch: config.max_batch < 2, an image size other than
+ * the configuration's, mmt_orb_capacity() above 16384. */
+int mmt_stereo_frame(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h,
+                     int stride, const int32_t* mask, mmt_kp* kps, uint8_t* desc, int cap, int* n,
+                     mmt_kp* kps_right, uint8_t* desc_right, int cap_right, int* n_right,
+                     float* uR, float* depth, int32_t* right_idx, int32_t* sem_label,
+                     mmt_stereo_counters* counters);
 
 /* Upper bound on keypoints per frame: the sum over levels of max(quota, 4 * nIni) + 8 slots, where
  * DistributeOctTree keeps at most max(quota + 2, 4 * nIni) keys. */

@@ -132,6 +132,19 @@ class MmtVocTrainStats(ctypes.Structure):
                [("iters", ctypes.c_int32 * 10)]
 
 
+STEREO_COUNTERS = ("n_coarse", "n_window_edge", "n_end_shift", "n_delta", "n_range", "n_clamped",
+                   "n_accepted", "n_median_removed", "median")
+
+
+class MmtStereoCounters(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_int32) for k in STEREO_COUNTERS] + [("th_dist", ctypes.c_float)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k in STEREO_COUNTERS}
+        d["th_dist"] = np.float32(self.th_dist)
+        return d
+
+
 MAP_DUMP_FIELDS = (("kf_i", np.int64, 4), ("kf_T", np.float32, 16), ("kf_mps_start", np.int32, 1),
                    ("kf_mps", np.int32, 1), ("pt_f", np.float32, 5), ("pt_i", np.int32, 5),
                    ("obs_start", np.int32, 1), ("obs_i", np.int32, 3), ("obs_f", np.float32, 4),
@@ -267,6 +280,11 @@ def lib():
         L.mmt_orb_extract_device.argtypes = [vp, vp, i32, sz, vp, vp, i32, vp, vp]
         L.mmt_orb_device_status.argtypes = [vp, vp]
         L.mmt_debug_orb_raise.argtypes = [vp, i32]
+        L.mmt_stereo_matches.argtypes = [vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp,
+                                         vp, vp, vp, vp, ctypes.POINTER(MmtStereoCounters)]
+        L.mmt_stereo_frame.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp, vp, vp,
+                                       i32, vp, vp, vp, vp, vp,
+                                       ctypes.POINTER(MmtStereoCounters)]
         L.mmt_debug_fetch.restype = ctypes.c_long
         L.mmt_debug_fetch.argtypes = [vp, i32, i32, vp, sz]
         L.mmt_reset.argtypes = [vp]
@@ -395,6 +413,59 @@ class Context:
         self._check(lib().mmt_orb_extract_batch(self._h, ptrs, nf, w, _p(kps), _p(desc), cap,
                                                 _p(ns)))
         return [(kps[i, :ns[i]].copy(), desc[i, :ns[i]].copy()) for i in range(nf)]
+
+    # -- stereo frames (System::TrackStereo's Frame constructor) -------------------------------
+    def stereo_matches(self, left, right, kps_left, desc_left, kps_right, desc_right):
+        """Frame::ComputeStereoMatches on caller-supplied keys of a rectified gray pair: dict of
+        uR, depth, right_idx, best_dist, sad (one entry per left key) and the counters."""
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        h, w = left.shape
+        assert right.shape == (h, w), "the pair differs in size"
+        kl = np.ascontiguousarray(kps_left, KP_DTYPE)
+        kr = np.ascontiguousarray(kps_right, KP_DTYPE)
+        dl = np.ascontiguousarray(desc_left, np.uint8).reshape(len(kl), 32)
+        dr = np.ascontiguousarray(desc_right, np.uint8).reshape(len(kr), 32)
+        n = len(kl)
+        uR = np.zeros(n, np.float32)
+        depth = np.zeros(n, np.float32)
+        ridx, best, sad = (np.zeros(n, np.int32) for _ in range(3))
+        c = MmtStereoCounters()
+        self._check(lib().mmt_stereo_matches(self._h, _p(left), _p(right), w, h, w, n, _p(kl),
+                                             _p(dl), len(kr), _p(kr), _p(dr), _p(uR), _p(depth),
+                                             _p(ridx), _p(best), _p(sad), ctypes.byref(c)))
+        return dict(uR=uR, depth=depth, right_idx=ridx, best_dist=best, sad=sad,
+                    counters=c.as_dict())
+
+    def stereo_frame(self, left, right, mask=None, cap=None):
+        """The stereo Frame constructor on a rectified gray pair (mask: optional int32 labels):
+        dict of kps, desc (left), kps_right, desc_right, uR, depth, right_idx, sem_label (zeros
+        without a mask) and the counters."""
+        left = np.ascontiguousarray(left, np.uint8)
+        right = np.ascontiguousarray(right, np.uint8)
+        h, w = left.shape
+        assert right.shape == (h, w), "the pair differs in size"
+        if mask is not None:
+            mask = np.ascontiguousarray(mask, np.int32)
+            assert mask.shape == (h, w)
+        cap = self.capacity() if cap is None else cap
+        k = [np.zeros(cap, KP_DTYPE) for _ in range(2)]
+        d = [np.zeros((cap, 32), np.uint8) for _ in range(2)]
+        uR = np.zeros(cap, np.float32)
+        depth = np.zeros(cap, np.float32)
+        ridx = np.zeros(cap, np.int32)
+        sem = np.zeros(cap, np.int32)
+        n, nr = ctypes.c_int(0), ctypes.c_int(0)
+        c = MmtStereoCounters()
+        self._check(lib().mmt_stereo_frame(self._h, _p(left), _p(right), w, h, w,
+                                           _p(mask) if mask is not None else None, _p(k[0]),
+                                           _p(d[0]), cap, ctypes.byref(n), _p(k[1]), _p(d[1]), cap,
+                                           ctypes.byref(nr), _p(uR), _p(depth), _p(ridx), _p(sem),
+                                           ctypes.byref(c)))
+        n, nr = n.value, nr.value
+        return dict(kps=k[0][:n].copy(), desc=d[0][:n].copy(), kps_right=k[1][:nr].copy(),
+                    desc_right=d[1][:nr].copy(), uR=uR[:n].copy(), depth=depth[:n].copy(),
+                    right_idx=ridx[:n].copy(), sem_label=sem[:n].copy(), counters=c.as_dict())
 
     # -- tracking (System::TrackRGBD) ---------------------------------------------------------
     def reset(self):

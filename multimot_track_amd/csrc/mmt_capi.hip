@@ -186,6 +186,7 @@ void mmt_destroy(mmt_ctx* ctx) {
   (void)hipFree(ctx->t_disp);
   (void)hipFree(ctx->t_flow);
   (void)hipFree(ctx->t_mask);
+  (void)hipFree(ctx->s_mask);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
   delete ctx;
 }
@@ -317,6 +318,182 @@ int mmt_debug_orb_raise(mmt_ctx* ctx, int flags) {
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     ctx->engine.raise_flags(flags, ctx->stream);
   });
+}
+
+// ---- stereo frames (Frame.cc:79-159, 849-1038) -------------------------------------------------
+static mmt::StereoLevels stereo_levels(const mmt_ctx* ctx) {
+  mmt::StereoLevels lv;
+  memset(&lv, 0, sizeof(lv));
+  const auto& L = ctx->engine.levels();
+  lv.nlevels = ctx->orb.nlevels;
+  lv.rows = ctx->cfg.height;
+  lv.cols = ctx->cfg.width;
+  for (int l = 0; l < lv.nlevels; l++) {
+    lv.w[l] = L[l].w;
+    lv.h[l] = L[l].h;
+    lv.off[l] = L[l].off;
+    lv.scale[l] = ctx->orb.scale[l];
+    lv.invScale[l] = ctx->orb.invScale[l];
+  }
+  return lv;
+}
+
+static void check_stereo_common(mmt_ctx* ctx, const char* who, int w, int h, int stride) {
+  if (w != ctx->cfg.width || h != ctx->cfg.height)
+    throw ArgError("image size differs from the context configuration");
+  if (stride < w) throw ArgError("stride < width");
+  if (ctx->cfg.max_batch < 2)
+    throw ArgError(std::string(who) + " needs config.max_batch >= 2: the device pyramid is "
+                   "frame-major per batch slot and a stereo pair takes two slots");
+  if (ctx->orb.nlevels > mmt::kStereoMaxLevels) throw ArgError("too many pyramid levels");
+}
+
+// The keys Frame::ComputeStereoMatches would index out of bounds with (pin (c) of mmt_stereo.hip),
+// tested with the float operations of the kernels.
+static void check_stereo_keys(const mmt::StereoLevels& lv, int nl, const mmt_kp* kl, int nr,
+                              const mmt_kp* kr) {
+  for (int i = 0; i < nl; i++) {
+    const mmt_kp& k = kl[i];
+    if (k.octave < 0 || k.octave >= lv.nlevels)
+      throw ArgError("left key " + std::to_string(i) + ": octave outside the pyramid");
+    const float s = lv.invScale[k.octave];
+    const float u = roundf(k.x * s), v = roundf(k.y * s);
+    if (!(u - 5.f >= 0.f && u + 5.f < (float)lv.w[k.octave] && v - 5.f >= 0.f &&
+          v + 5.f < (float)lv.h[k.octave] && k.y >= 0.f && k.y < (float)lv.rows))
+      throw ArgError("left key " + std::to_string(i) + ": its 11 x 11 window leaves its level");
+  }
+  for (int i = 0; i < nr; i++) {
+    const mmt_kp& k = kr[i];
+    if (k.octave < 0 || k.octave >= lv.nlevels)
+      throw ArgError("right key " + std::to_string(i) + ": octave outside the pyramid");
+    const float r = 1.2f * lv.scale[k.octave];
+    const float top = k.y + r, bot = k.y - r;
+    if (!(floorf(bot) >= 0.f && ceilf(top) < (float)lv.rows))
+      throw ArgError("right key " + std::to_string(i) + ": its row range leaves the image");
+  }
+}
+
+static void stage_pair(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, int stride) {
+  const int w = ctx->cfg.width, h = ctx->cfg.height;
+  ensure_staging(ctx, 2);
+  const size_t fb = (size_t)w * h;
+  MMT_HIP(hipMemcpy2DAsync(ctx->d_in, w, left, stride, w, h, hipMemcpyHostToDevice, ctx->stream));
+  MMT_HIP(hipMemcpy2DAsync(ctx->d_in + fb, w, right, stride, w, h, hipMemcpyHostToDevice,
+                           ctx->stream));
+}
+
+int mmt_stereo_matches(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h,
+                       int stride, int n_left, const mmt_kp* kps_left, const uint8_t* desc_left,
+                       int n_right, const mmt_kp* kps_right, const uint8_t* desc_right, float* uR,
+                       float* depth, int32_t* right_idx, int32_t* best_dist, int32_t* sad,
+                       mmt_stereo_counters* counters) {
+  if (!ctx || !left || !right || !uR || !depth || !right_idx || !counters) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_stereo_common(ctx, "mmt_stereo_matches", w, h, stride);
+    if (n_left < 0 || n_left > mmt::kMaxMatchKeys || n_right < 0 || n_right > mmt::kMaxMatchKeys)
+      throw ArgError("key count outside [0, 16384]");
+    if ((n_left > 0 && (!kps_left || !desc_left)) || (n_right > 0 && (!kps_right || !desc_right)))
+      throw ArgError("null key arrays");
+    const mmt::StereoLevels lv = stereo_levels(ctx);
+    check_stereo_keys(lv, n_left, kps_left, n_right, kps_right);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    stage_pair(ctx, left, right, stride);
+    ctx->engine.build_pyramids(ctx->d_in, 2, (size_t)w * h, s);
+    DevBuf<mmt_kp> kl(n_left), kr(n_right);
+    DevBuf<uint8_t> dl((size_t)32 * n_left), dr((size_t)32 * n_right);
+    DevBuf<int> dn(2);
+    const int ns[2] = {n_left, n_right};
+    MMT_HIP(hipMemcpyAsync(dn.p, ns, sizeof(ns), hipMemcpyHostToDevice, s));
+    if (n_left > 0) {
+      MMT_HIP(hipMemcpyAsync(kl.p, kps_left, sizeof(mmt_kp) * (size_t)n_left, hipMemcpyHostToDevice, s));
+      MMT_HIP(hipMemcpyAsync(dl.p, desc_left, (size_t)32 * n_left, hipMemcpyHostToDevice, s));
+    }
+    if (n_right > 0) {
+      MMT_HIP(hipMemcpyAsync(kr.p, kps_right, sizeof(mmt_kp) * (size_t)n_right, hipMemcpyHostToDevice, s));
+      MMT_HIP(hipMemcpyAsync(dr.p, desc_right, (size_t)32 * n_right, hipMemcpyHostToDevice, s));
+    }
+    mmt::StereoMatcher& M = ctx->stereo;
+    M.ensure(h, std::max(std::max(n_left, n_right), 1), ctx->orb.scale[ctx->orb.nlevels - 1]);
+    const mmt::StereoSide L{ctx->engine.pyramid(), kl.p, dl.p, dn.p};
+    const mmt::StereoSide R{ctx->engine.pyramid() + ctx->engine.pyramid_stride(), kr.p, dr.p,
+                            dn.p + 1};
+    M.run(lv, L, R, n_left, n_right, ctx->cfg.bf, s);
+    if (n_left > 0) {
+      const size_t nb = sizeof(float) * (size_t)n_left;
+      MMT_HIP(hipMemcpyAsync(uR, M.uR, nb, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(depth, M.depth, nb, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(right_idx, M.right_idx, nb, hipMemcpyDeviceToHost, s));
+      if (best_dist) MMT_HIP(hipMemcpyAsync(best_dist, M.best_dist, nb, hipMemcpyDeviceToHost, s));
+      if (sad) MMT_HIP(hipMemcpyAsync(sad, M.sad, nb, hipMemcpyDeviceToHost, s));
+    }
+    MMT_HIP(hipMemcpyAsync(counters, M.counters, sizeof(*counters), hipMemcpyDeviceToHost, s));
+    MMT_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int mmt_stereo_frame(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, int w, int h,
+                     int stride, const int32_t* mask, mmt_kp* kps, uint8_t* desc, int cap, int* n,
+                     mmt_kp* kps_right, uint8_t* desc_right, int cap_right, int* n_right,
+                     float* uR, float* depth, int32_t* right_idx, int32_t* sem_label,
+                     mmt_stereo_counters* counters) {
+  if (!ctx || !left || !right || !kps || !desc || !n || !kps_right || !desc_right || !n_right ||
+      !uR || !depth || !right_idx || !counters || (mask && !sem_label))
+    return MMT_EINVAL;
+  bool short_cap = false;
+  const int rc = guard(ctx, [&] {
+    check_stereo_common(ctx, "mmt_stereo_frame", w, h, stride);
+    if (cap < 0 || cap_right < 0) throw ArgError("negative capacity");
+    const int ecap = ctx->engine.capacity();
+    if (ecap > mmt::kMaxMatchKeys)
+      throw ArgError("mmt_orb_capacity() above 16384 keys: too many for the stereo matcher");
+    const mmt::StereoLevels lv = stereo_levels(ctx);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const size_t fb = (size_t)w * h;
+    mmt::StereoMatcher& M = ctx->stereo;
+    M.ensure(h, ecap, ctx->orb.scale[ctx->orb.nlevels - 1]);
+    if (mask && !ctx->s_mask) MMT_HIP(hipMalloc((void**)&ctx->s_mask, fb * sizeof(int32_t)));
+    stage_pair(ctx, left, right, stride);
+    if (mask)
+      MMT_HIP(hipMemcpyAsync(ctx->s_mask, mask, fb * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    // extraction, matching and the median stage back to back on the stream
+    ctx->engine.run(ctx->d_in, 2, fb, ctx->d_kps, ctx->d_desc, ecap, ctx->d_n, s);
+    const mmt::StereoSide L{ctx->engine.pyramid(), ctx->d_kps, ctx->d_desc, ctx->d_n};
+    const mmt::StereoSide R{ctx->engine.pyramid() + ctx->engine.pyramid_stride(),
+                            ctx->d_kps + ecap, ctx->d_desc + (size_t)32 * ecap, ctx->d_n + 1};
+    M.run(lv, L, R, ecap, ecap, ctx->cfg.bf, s);
+    if (mask) M.sem_labels(L, ecap, ctx->s_mask, w, h, s);
+    int counts[2] = {0, 0};
+    MMT_HIP(hipMemcpyAsync(counts, ctx->d_n, sizeof(counts), hipMemcpyDeviceToHost, s));
+    ctx->engine.check_flags(s);  // synchronises the stream
+    *n = counts[0];
+    *n_right = counts[1];
+    if (counts[0] > cap || counts[1] > cap_right) {
+      short_cap = true;
+      return;
+    }
+    const size_t nl = (size_t)counts[0], nr = (size_t)counts[1];
+    if (nl > 0) {
+      MMT_HIP(hipMemcpyAsync(kps, L.kps, sizeof(mmt_kp) * nl, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(desc, L.desc, 32 * nl, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(uR, M.uR, 4 * nl, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(depth, M.depth, 4 * nl, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(right_idx, M.right_idx, 4 * nl, hipMemcpyDeviceToHost, s));
+      if (mask) MMT_HIP(hipMemcpyAsync(sem_label, M.sem, 4 * nl, hipMemcpyDeviceToHost, s));
+    }
+    if (nr > 0) {
+      MMT_HIP(hipMemcpyAsync(kps_right, R.kps, sizeof(mmt_kp) * nr, hipMemcpyDeviceToHost, s));
+      MMT_HIP(hipMemcpyAsync(desc_right, R.desc, 32 * nr, hipMemcpyDeviceToHost, s));
+    }
+    MMT_HIP(hipMemcpyAsync(counters, M.counters, sizeof(*counters), hipMemcpyDeviceToHost, s));
+    MMT_HIP(hipStreamSynchronize(s));
+  });
+  if (rc == MMT_OK && short_cap) {
+    ctx->err = "keypoint capacity too small";
+    return MMT_ENOSPC;
+  }
+  return rc;
 }
 
 static void ensure_tracker(mmt_ctx* ctx) {

@@ -6,6 +6,7 @@
 #include "mmt_ba.h"
 #include "mmt_bow.h"
 #include "mmt_internal.h"
+#include "mmt_stereo.h"
 #include "mmt_tracker.h"
 
 struct mmt_ctx {
@@ -21,6 +22,8 @@ struct mmt_ctx {
   uint8_t* d_desc = nullptr;
   int* d_n = nullptr;
   int staged_frames = 0;
+  mmt::StereoMatcher stereo;    // mmt_stereo_matches / mmt_stereo_frame (workspace kept across calls)
+  int32_t* s_mask = nullptr;    // mmt_stereo_frame's semantic mask on the device
   // tracking (one sequence per context)
   mmt::Tracker tracker;
   bool tracker_ready = false;

@@ -88,6 +88,8 @@ class OrbEngine {
   // d_gray: nframes x frame_pitch bytes, row pitch = width.  Outputs device pointers.
   void run(const uint8_t* d_gray, int nframes, size_t frame_pitch, mmt_kp* d_kps,
            uint8_t* d_desc, int cap_per_frame, int* d_n, hipStream_t stream);
+  // The pyramid stage of run() alone: levels 0.. of nframes gray frames into the pyramid buffer.
+  void build_pyramids(const uint8_t* d_gray, int nframes, size_t frame_pitch, hipStream_t stream);
   int capacity() const { return cap_frame_; }
   int width() const { return w_; }
   int height() const { return h_; }
@@ -123,6 +125,7 @@ class OrbEngine {
   // (GPU_MAX_HW_QUEUES), and streams beyond them end up sharing the caller's queue.
   hipStream_t side_ = nullptr;
   hipEvent_t ev_pyr_ = nullptr, ev_blur_ = nullptr, ev_gray_ = nullptr;
+  void launch_pyramid(uint8_t* pyr, int nframes, hipStream_t st);
   void run_part(int f0, int nf, hipStream_t st_main, hipStream_t st_side, hipEvent_t* ev,
                 mmt_kp* d_kps, uint8_t* d_desc, int cap_per_frame, int* d_n);
   int iniTh_ = 20, minTh_ = 7;

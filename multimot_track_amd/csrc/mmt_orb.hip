@@ -2108,6 +2108,41 @@ void OrbEngine::run(const uint8_t* d_gray, int nframes, size_t frame_pitch, mmt_
   MMT_HIP(hipGetLastError());
 }
 
+// Levels 1.. of frames [0, nframes) of the pyramid at `pyr` (level 0 in place): one k_pyramid
+// launch, or the k_resize chain.
+void OrbEngine::launch_pyramid(uint8_t* pyr, int nframes, hipStream_t st) {
+  auto resize = [&](int l) {
+    const LevelInfo& S = lv_[l - 1];
+    const LevelInfo& L = lv_[l];
+    dim3 grid((L.w + kResizeCols - 1) / kResizeCols, (L.h + kResizeRows - 1) / kResizeRows,
+              nframes);
+    hipLaunchKernelGGL(k_resize, grid, dim3(256), rs_lds_[l], st, pyr, pyr_stride_, S.off,
+                       S.w, L.off, L.w, L.h, d_xtab_ + xtab_off_[l], d_ytab_ + ytab_off_[l],
+                       rs_pitch_[l], xcd_order_ & 1);
+  };
+  // k_pyramid for small batches, where the chain's seven launches are pure latency; from 64
+  // frames on the chain is faster (at 128: 151 against 220 us standalone, the band workgroups'
+  // per-level barriers and halo rows cost more than the launches; mmt_internal.h)
+  if (pyr_bands_ > 0 && nframes <= pyr_max_frames_) {
+    hipLaunchKernelGGL(k_pyramid, dim3(pyr_bands_, nframes), dim3(1024), pyr_lds_,
+                       st, pyr, pyr_stride_, d_lv_, d_xtab_, d_ytab_, d_pyr_bands_, pyr_args_);
+  } else {
+    for (int l = 1; l < nlevels_; l++) resize(l);
+  }
+}
+
+// The pyramid stage alone (no FAST): the unblurred pyramids of nframes gray frames, left in the
+// engine's pyramid buffer as run() leaves them (the stereo matcher's windows, Frame.cc:960).
+void OrbEngine::build_pyramids(const uint8_t* d_gray, int nframes, size_t frame_pitch,
+                               hipStream_t stream) {
+  if (nframes < 1 || nframes > max_batch_) throw ArgError("nframes outside [1, max_batch]");
+  if (d_gray != d_pyr_ || frame_pitch != pyr_stride_)
+    MMT_HIP(hipMemcpy2DAsync(d_pyr_, pyr_stride_, d_gray, frame_pitch, (size_t)w_ * h_, nframes,
+                             hipMemcpyDeviceToDevice, stream));
+  launch_pyramid(d_pyr_, nframes, stream);
+  MMT_HIP(hipGetLastError());
+}
+
 // The launch sequence of frames [f0, f0 + nf) of the batch on a (main, side) stream pair: every
 // per-frame buffer is frame-major, so the part's launches see its frames as frames 0..nf-1 of
 // views offset by f0.  ev: the part's events (nullptr: the engine's own).
@@ -2149,26 +2184,7 @@ void OrbEngine::run_part(int f0, int nframes, hipStream_t stream, hipStream_t si
                        cellcnt, total_slots_, lkeys, knode, kq, okeys, out_slots_, ocount,
                        nlevels_, node_cap_, two ? key_cap1_ : key_cap_, l0, d_err_);
   };
-  auto resize = [&](int l, hipStream_t st) {
-    const LevelInfo& S = lv_[l - 1];
-    const LevelInfo& L = lv_[l];
-    dim3 grid((L.w + kResizeCols - 1) / kResizeCols, (L.h + kResizeRows - 1) / kResizeRows,
-              nframes);
-    hipLaunchKernelGGL(k_resize, grid, dim3(256), rs_lds_[l], st, pyr, pyr_stride_, S.off,
-                       S.w, L.off, L.w, L.h, d_xtab_ + xtab_off_[l], d_ytab_ + ytab_off_[l],
-                       rs_pitch_[l], xcd_order_ & 1);
-  };
-  auto pyramid = [&](hipStream_t st) {  // levels 1..: one k_pyramid launch, or the k_resize chain
-    // k_pyramid for small batches, where the chain's seven launches are pure latency; from 64
-    // frames on the chain is faster (at 128: 151 against 220 us standalone, the band workgroups'
-    // per-level barriers and halo rows cost more than the launches; mmt_internal.h)
-    if (pyr_bands_ > 0 && nframes <= pyr_max_frames_) {
-      hipLaunchKernelGGL(k_pyramid, dim3(pyr_bands_, nframes), dim3(1024), pyr_lds_,
-                         st, pyr, pyr_stride_, d_lv_, d_xtab_, d_ytab_, d_pyr_bands_, pyr_args_);
-    } else {
-      for (int l = 1; l < nlevels_; l++) resize(l, st);
-    }
-  };
+  auto pyramid = [&](hipStream_t st) { launch_pyramid(pyr, nframes, st); };
   auto blur = [&](hipStream_t st) {
     hipLaunchKernelGGL(k_blur, dim3((ntiles_ + 3) / 4, nframes), dim3(256), 0, st, pyr,
                        blurb, pyr_stride_, d_lv_, d_tiles_, ntiles_, (xcd_order_ >> 1) & 1);
