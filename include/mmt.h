@@ -58,6 +58,11 @@
  *   mmt_stereo_frame    <- System::TrackStereo -> Tracking::GrabImageStereo's stereo Frame
  *                          constructor Frame.cc:79-159
  *   mmt_stereo_matches  <- Frame::ComputeStereoMatches Frame.cc:849-1038
+ *   mmt_sim3solver_iterate
+ *                       <- Sim3Solver::SetRansacParameters + iterate, Sim3Solver.cc:114-364
+ *                          (LoopClosing::ComputeSim3 LoopClosing.cc:276-303), a batch of solvers
+ *   mmt_search_by_sim3  <- ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
+ *                          ORBmatcher.cc:1477-1701 (LoopClosing.cc:325)
  *   mmt_destroy         <- System::Shutdown / delete
  */
 #ifndef MMT_H
@@ -542,6 +547,97 @@ int mmt_search_by_projection_keyframe(mmt_ctx* ctx, const mmt_match_frame* cur,
                                       const mmt_keyframe_points* points, const uint8_t* skip,
                                       float th, int orb_dist, const uint8_t* bound_in,
                                       int32_t* match_out, int* nmatches, int* n_rescan);
+
+/* ---- Loop-closure geometry: LoopClosing::ComputeSim3's steps 2 and 3 (LoopClosing.cc:227-420) ---
+ * Sim3Solver(pKF1, pKF2, vpMatched12, bFixScale) + SetRansacParameters(probability, minInliers,
+ * maxIterations) + iterate(nIterations, bNoMore, vbInliers, nInliers) (reference
+ * src/Sim3Solver.cc:37-364; ComputeSim3 uses (0.99, 20, 300) and rounds of iterate(5) over its
+ * candidate keyframes), for a batch of independent solvers: one call runs one round of every
+ * candidate.  At most 64 solvers, 16384 correspondences per solver and 300 iterations per call.
+ *
+ * A problem holds the constructor's products in correspondence order (the order of mvX3Dc1):
+ * X1 / X2 n x 3 = mvX3Dc1 / mvX3Dc2 (the matched points in camera 1 / camera 2), sigma2_1 /
+ * sigma2_2 n = mvLevelSigma2[octave] of the two keys, the two cameras and bFixScale.  The entry
+ * point derives mvnMaxError1 / 2 (9.210 sigma2 as the reference's vector<size_t> holds it) and
+ * mvP1im1 / mvP2im2 (FromCameraToImage).
+ *
+ * Random minimal sets: randi[i][3 k + j] = DUtils::Random::RandomInt(0, n - 1 - j) of draw j in
+ * iteration k of this call for solver i, the caller's stream as in mmt_pnpsolver_iterate;
+ * n_draw_iters[i] must cover min(n_iterations, maxIts - state.iterations), maxIts being
+ * SetRansacParameters' cap.  A solver with n < min_inliers returns no_more and reads no draw.
+ *
+ * The solver's state across calls (mnIterations, mnBestInliers, mBestT12, mBestRotation,
+ * mBestTranslation, mBestScale, mvbBestInliers) is states[i], caller-owned (best_mask: n bytes);
+ * zeroed it is a new solver.
+ *
+ * results[i]: found = iterate() returned a matrix, then T12 (row-major mBestT12), inliers (n
+ * bytes, correspondence order; mapping through mvnIndices1 is the caller's) and n_inliers;
+ * no_more = bNoMore.  probes (optional, n_solvers entries; test hook without a reference
+ * counterpart): counts / flags (cap x n bytes) / T12 (cap x 16) of the first n_hyp <= cap
+ * hypotheses the call launched for the solver, whether or not iterate()'s loop reached them.
+ * Choices where the reference leaves the arithmetic to OpenCV: DESIGN.md section 2. */
+typedef struct mmt_sim3_problem {
+  int n;
+  const float* X1;         /* n x 3 */
+  const float* X2;         /* n x 3 */
+  const float* sigma2_1;   /* n     */
+  const float* sigma2_2;   /* n     */
+  float fx1, fy1, cx1, cy1;  /* mK1 */
+  float fx2, fy2, cx2, cy2;  /* mK2 */
+  int fix_scale;           /* mbFixScale                                                   */
+  double probability;      /* mRansacProb                                                  */
+  int min_inliers;         /* mRansacMinInliers                                            */
+  int max_iterations;      /* SetRansacParameters' maxIterations                           */
+} mmt_sim3_problem;
+
+typedef struct mmt_sim3_state {
+  int iterations;          /* mnIterations                                                 */
+  int best_inliers;        /* mnBestInliers                                                */
+  float best_T12[16];      /* mBestT12 (row-major)                                         */
+  float best_R[9];         /* mBestRotation                                                */
+  float best_t[3];         /* mBestTranslation                                             */
+  float best_scale;        /* mBestScale                                                   */
+  uint8_t* best_mask;      /* mvbBestInliers, n bytes                                      */
+} mmt_sim3_state;
+
+typedef struct mmt_sim3_result {
+  int found, n_inliers, no_more;
+  float T12[16];
+  uint8_t* inliers;        /* n bytes */
+} mmt_sim3_result;
+
+typedef struct mmt_sim3_probe {
+  int cap, n_hyp;
+  int32_t* counts;         /* cap      */
+  uint8_t* flags;          /* cap x n  */
+  float* T12;              /* cap x 16 */
+} mmt_sim3_probe;
+
+int mmt_sim3solver_iterate(mmt_ctx* ctx, int n_solvers, const mmt_sim3_problem* problems,
+                           const int32_t* const* randi, const int32_t* n_draw_iters,
+                           int n_iterations, mmt_sim3_state* states, mmt_sim3_result* results,
+                           mmt_sim3_probe* probes);
+
+/* ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) (ORBmatcher.cc:1477-1701;
+ * LoopClosing.cc:325 with th 7.5).  Each keyframe is a mmt_match_frame (keys, descriptors, grid,
+ * Tcw) with its map points in mvpMapPoints order (points->m == kf->n; angle unused) and a skip
+ * byte per slot (empty, or the point is bad).  matched12_in (n1): -1 no prior match, k >= 0 a
+ * match to the point at key k of keyframe 2, -2 a match to a point keyframe 2 does not hold (sets
+ * vbAlreadyMatched1 only, :1514).  Every unmatched point of keyframe 1 is moved into camera 2
+ * (R1w Xw + t1w, then sR21, t21) and searched among keyframe 2's keys, and the reverse: depth not
+ * negative, KeyFrame::IsInImage, the scale-invariance distances on cv::norm of the camera-frame
+ * point, PredictScale, the window th * scale[level], keys at the predicted level or one below, the
+ * closest descriptor (first of equal distances) if its distance is <= TH_HIGH (100).  No
+ * viewing-angle or reprojection-error test.  match_out[i1] (n1) = the keyframe-2 key whose point
+ * is newly matched (both directions agree), else -1; *n_found = the return value; cand1_out (n1) /
+ * cand2_out (n2), optional = vnMatch1 / vnMatch2 before the agreement pass.  Camera (pKF1's, as
+ * the reference uses for both directions) and image bounds from the context's configuration. */
+int mmt_search_by_sim3(mmt_ctx* ctx, const mmt_match_frame* kf1,
+                       const mmt_keyframe_points* points1, const uint8_t* skip1,
+                       const mmt_match_frame* kf2, const mmt_keyframe_points* points2,
+                       const uint8_t* skip2, float s12, const float* R12, const float* t12,
+                       float th, const int32_t* matched12_in, int32_t* match_out, int* n_found,
+                       int32_t* cand1_out, int32_t* cand2_out);
 
 /* A keyframe as SearchForTriangulation reads it: mvKeysUn, mDescriptors, mvuRight (< 0: monocular),
  * mFeatVec, whether mvpMapPoints[i] holds a MapPoint, and Tcw (row-major). */

@@ -218,6 +218,32 @@ class MmtKeyFramePoints(ctypes.Structure):
                 ("angle", ctypes.c_void_p)]
 
 
+class MmtSim3Problem(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("X1", ctypes.c_void_p), ("X2", ctypes.c_void_p),
+                ("sigma2_1", ctypes.c_void_p), ("sigma2_2", ctypes.c_void_p)] + \
+               [(k, ctypes.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2",
+                                              "cy2")] + \
+               [("fix_scale", ctypes.c_int), ("probability", ctypes.c_double),
+                ("min_inliers", ctypes.c_int), ("max_iterations", ctypes.c_int)]
+
+
+class MmtSim3State(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("best_inliers", ctypes.c_int),
+                ("best_T12", ctypes.c_float * 16), ("best_R", ctypes.c_float * 9),
+                ("best_t", ctypes.c_float * 3), ("best_scale", ctypes.c_float),
+                ("best_mask", ctypes.c_void_p)]
+
+
+class MmtSim3Result(ctypes.Structure):
+    _fields_ = [("found", ctypes.c_int), ("n_inliers", ctypes.c_int), ("no_more", ctypes.c_int),
+                ("T12", ctypes.c_float * 16), ("inliers", ctypes.c_void_p)]
+
+
+class MmtSim3Probe(ctypes.Structure):
+    _fields_ = [("cap", ctypes.c_int), ("n_hyp", ctypes.c_int), ("counts", ctypes.c_void_p),
+                ("flags", ctypes.c_void_p), ("T12", ctypes.c_void_p)]
+
+
 class MmtSftKeyFrame(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p),
                 ("uR", ctypes.c_void_p), ("has_mp", ctypes.c_void_p), ("fv", MmtFeatureVector),
@@ -318,6 +344,12 @@ def lib():
                                           ctypes.POINTER(MmtLocalPoints), ctypes.c_float, vp, vp]
         L.mmt_local_bundle_adjustment.argtypes = [vp, ctypes.POINTER(MmtBAProblem), vp, vp, vp,
                                                   vp]
+        L.mmt_sim3solver_iterate.argtypes = [vp, i32, vp, vp, vp, i32, vp, vp, vp]
+        L.mmt_search_by_sim3.argtypes = [vp, ctypes.POINTER(MmtMatchFrame),
+                                         ctypes.POINTER(MmtKeyFramePoints), vp,
+                                         ctypes.POINTER(MmtMatchFrame),
+                                         ctypes.POINTER(MmtKeyFramePoints), vp, ctypes.c_float,
+                                         vp, vp, ctypes.c_float, vp, vp, vp, vp, vp]
         L.mmt_map_counters_read.argtypes = [vp, ctypes.POINTER(MmtMapCounters)]
         L.mmt_map_dump.argtypes = [vp, vp, ctypes.POINTER(MmtMapDumpArrays)]
         L.mmt_set_keyframe_culling_ratio.argtypes = [vp, ctypes.c_double]
@@ -719,6 +751,131 @@ class Context:
         self._check(lib().mmt_fuse_candidates(self._h, ctypes.byref(fr), ctypes.byref(P),
                                               ctypes.c_float(th), _p(idx), _p(dist)))
         return idx[:m], dist[:m]
+
+    # ---- loop-closure geometry (LoopClosing::ComputeSim3's Sim3Solver and SearchBySim3) ----
+    def sim3solver_iterate(self, problems, randi, n_iterations=5, states=None, probe=False):
+        """Sim3Solver::SetRansacParameters + iterate(n_iterations) for a batch of solvers.
+        problems: dicts(X1, X2, sigma2_1, sigma2_2, K1, K2, fix_scale[, probability 0.99,
+        min_inliers 20, max_iterations 300]); randi: per solver the caller's RandomInt draws
+        (iterations x 3); states: per solver a dict(iterations, best_inliers, best_T12, best_R,
+        best_t, best_scale, best_mask), updated in place ({}: a new solver).  Returns per solver
+        dict(found, no_more, n_inliers, T12, mask); with probe also hyp_counts / hyp_flags /
+        hyp_T12 of every hypothesis the call launched (test hook)."""
+        ns = len(problems)
+        if states is None:
+            states = [{} for _ in range(ns)]
+        keep = []
+        P = (MmtSim3Problem * max(ns, 1))()
+        S = (MmtSim3State * max(ns, 1))()
+        R = (MmtSim3Result * max(ns, 1))()
+        B = (MmtSim3Probe * max(ns, 1))()
+        RI = (ctypes.c_void_p * max(ns, 1))()
+        ND = np.zeros(max(ns, 1), np.int32)
+        masks, outs, probes = [], [], []
+        for i, (pr, st) in enumerate(zip(problems, states)):
+            arrs = [np.ascontiguousarray(pr[k], np.float32)
+                    for k in ("X1", "X2", "sigma2_1", "sigma2_2")]
+            keep += arrs
+            n = len(arrs[2])
+            P[i].n = n
+            P[i].X1, P[i].X2, P[i].sigma2_1, P[i].sigma2_2 = [a.ctypes.data for a in arrs]
+            P[i].fx1, P[i].fy1, P[i].cx1, P[i].cy1 = pr["K1"]
+            P[i].fx2, P[i].fy2, P[i].cx2, P[i].cy2 = pr["K2"]
+            P[i].fix_scale = int(bool(pr["fix_scale"]))
+            P[i].probability = pr.get("probability", 0.99)
+            P[i].min_inliers = pr.get("min_inliers", 20)
+            P[i].max_iterations = pr.get("max_iterations", 300)
+            bm = np.zeros(max(n, 1), np.uint8)
+            bm[:n] = np.asarray(st.get("best_mask", np.zeros(n, bool)), np.uint8)[:n]
+            S[i].iterations = st.get("iterations", 0)
+            S[i].best_inliers = st.get("best_inliers", 0)
+            for name, size in (("best_T12", 16), ("best_R", 9), ("best_t", 3)):
+                getattr(S[i], name)[:] = np.asarray(st.get(name, np.zeros(size)),
+                                                    np.float32).reshape(size).tolist()
+            S[i].best_scale = float(st.get("best_scale", 0.0))
+            S[i].best_mask = bm.ctypes.data
+            out = np.zeros(max(n, 1), np.uint8)
+            R[i].inliers = out.ctypes.data
+            ri = np.ascontiguousarray(randi[i], np.int32).reshape(-1, 3)
+            keep.append(ri)
+            RI[i] = ri.ctypes.data
+            ND[i] = len(ri)
+            masks.append(bm)
+            outs.append(out)
+            if probe:
+                cap = max(int(n_iterations), 1)
+                pc = np.zeros(cap, np.int32)
+                pf = np.zeros((cap, max(n, 1)), np.uint8)
+                pt = np.zeros((cap, 4, 4), np.float32)
+                B[i].cap = cap
+                B[i].counts, B[i].flags, B[i].T12 = pc.ctypes.data, pf.ctypes.data, pt.ctypes.data
+                probes.append((pc, pf, pt))
+        self._check(lib().mmt_sim3solver_iterate(
+            self._h, ns, ctypes.addressof(P), ctypes.addressof(RI), _p(ND), int(n_iterations),
+            ctypes.addressof(S), ctypes.addressof(R), ctypes.addressof(B) if probe else None))
+        res = []
+        for i, st in enumerate(states):
+            n = P[i].n
+            st.update(iterations=S[i].iterations, best_inliers=S[i].best_inliers,
+                      best_T12=np.array(S[i].best_T12[:], np.float32).reshape(4, 4),
+                      best_R=np.array(S[i].best_R[:], np.float32).reshape(3, 3),
+                      best_t=np.array(S[i].best_t[:], np.float32),
+                      best_scale=np.float32(S[i].best_scale),
+                      best_mask=masks[i][:n].astype(bool))
+            r = dict(found=bool(R[i].found), no_more=bool(R[i].no_more),
+                     n_inliers=R[i].n_inliers,
+                     T12=np.array(R[i].T12[:], np.float32).reshape(4, 4),
+                     mask=outs[i][:n].astype(bool))
+            if probe:
+                pc, pf, pt = probes[i]
+                m = B[i].n_hyp
+                r.update(hyp_counts=pc[:m].copy(),
+                         hyp_flags=pf.reshape(-1)[:m * n].reshape(m, n).astype(bool),
+                         hyp_T12=pt[:m].copy())
+            res.append(r)
+        return res
+
+    def search_by_sim3(self, kf1, kf2, s12, R12, t12, th=7.5, matched12=None):
+        """ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th).  A keyframe is a
+        dict(kps, desc, depth, Tcw, Xw, min_dist, max_dist, pdesc, skip): its keys and its map
+        points in mvpMapPoints order (skip: empty slot or bad point).  matched12 (n1): -1 none,
+        k >= 0 the point at key k of keyframe 2, -2 a point keyframe 2 does not hold.  Returns
+        (n_found, match[key of kf1] = newly matched key of kf2 or -1, vnMatch1, vnMatch2)."""
+        keep = []
+        frames, points, skips = [], [], []
+        for kf in (kf1, kf2):
+            fr = self._match_frame(kf["kps"], kf["desc"], kf["depth"], kf["Tcw"], keep)
+            arrs = [np.ascontiguousarray(kf[k], np.float32) for k in ("Xw", "min_dist",
+                                                                      "max_dist")]
+            pd = np.ascontiguousarray(kf["pdesc"], np.uint8)
+            sk = np.ascontiguousarray(kf["skip"], np.uint8)
+            if len(sk) != fr.n or len(arrs[1]) != fr.n or len(pd) != fr.n:
+                raise ValueError("a keyframe's point arrays follow its keys")
+            ang = np.zeros(max(fr.n, 1), np.float32)
+            keep += arrs + [pd, sk, ang]
+            P = MmtKeyFramePoints()
+            P.m = fr.n
+            P.Xw, P.min_dist, P.max_dist = [a.ctypes.data for a in arrs]
+            P.desc, P.angle = pd.ctypes.data, ang.ctypes.data
+            frames.append(fr)
+            points.append(P)
+            skips.append(sk)
+        n1, n2 = frames[0].n, frames[1].n
+        m12 = np.full(max(n1, 1), -1, np.int32)
+        if matched12 is not None:
+            m12[:n1] = np.asarray(matched12, np.int32)
+        R = np.ascontiguousarray(R12, np.float32).reshape(9)
+        t = np.ascontiguousarray(t12, np.float32).reshape(3)
+        match = np.full(max(n1, 1), -1, np.int32)
+        c1 = np.full(max(n1, 1), -1, np.int32)
+        c2 = np.full(max(n2, 1), -1, np.int32)
+        nf = ctypes.c_int(0)
+        self._check(lib().mmt_search_by_sim3(
+            self._h, ctypes.byref(frames[0]), ctypes.byref(points[0]), skips[0].ctypes.data,
+            ctypes.byref(frames[1]), ctypes.byref(points[1]), skips[1].ctypes.data,
+            ctypes.c_float(s12), _p(R), _p(t), ctypes.c_float(th), _p(m12), _p(match),
+            ctypes.byref(nf), _p(c1), _p(c2)))
+        return nf.value, match[:n1], c1[:n1], c2[:n2]
 
     def local_bundle_adjustment(self, P):
         """Optimizer::LocalBundleAdjustment's solve on a problem dict (keys T, fixed, X, pt, kf,

@@ -14,6 +14,7 @@
 #include "mmt_ctx.h"
 #include "mmt_match.h"
 #include "mmt_pnp.h"
+#include "mmt_sim3.h"
 #include "mmt_track.h"
 #include "mmt_voctrain.h"
 
@@ -977,6 +978,137 @@ int mmt_fuse_candidates(mmt_ctx* ctx, const mmt_match_frame* kf, const mmt_local
       best_idx[j] = ho[j].x;
       best_dist[j] = ho[j].y;
     }
+  });
+}
+
+int mmt_search_by_sim3(mmt_ctx* ctx, const mmt_match_frame* kf1,
+                       const mmt_keyframe_points* points1, const uint8_t* skip1,
+                       const mmt_match_frame* kf2, const mmt_keyframe_points* points2,
+                       const uint8_t* skip2, float s12, const float* R12, const float* t12,
+                       float th, const int32_t* matched12_in, int32_t* match_out, int* n_found,
+                       int32_t* cand1_out, int32_t* cand2_out) {
+  if (!ctx || !kf1 || !kf2 || !points1 || !points2 || !R12 || !t12 || !n_found) return MMT_EINVAL;
+  const mmt_match_frame* kf[2] = {kf1, kf2};
+  const mmt_keyframe_points* pts[2] = {points1, points2};
+  const uint8_t* skip[2] = {skip1, skip2};
+  for (int d = 0; d < 2; d++)
+    if (pts[d]->m != kf[d]->n || (pts[d]->m > 0 && (!skip[d] || !pts[d]->Xw || !pts[d]->min_dist ||
+                                                    !pts[d]->max_dist || !pts[d]->desc)))
+      return MMT_EINVAL;
+  if (kf1->n > 0 && (!matched12_in || !match_out)) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_match_frame(ctx, kf1, true);
+    check_match_frame(ctx, kf2, true);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const int n[2] = {kf1->n, kf2->n};
+    // vbAlreadyMatched1 / 2 (ORBmatcher.cc:1504-1517)
+    std::vector<uint8_t> done[2] = {std::vector<uint8_t>(n[0], 0), std::vector<uint8_t>(n[1], 0)};
+    for (int i = 0; i < n[0]; i++) {
+      const int m = matched12_in[i];
+      if (m == -1) continue;
+      done[0][i] = 1;
+      if (m >= 0 && m < n[1]) done[1][m] = 1;
+    }
+    DevMatchFrame F1(ctx, kf1, true), F2(ctx, kf2, true);
+    const DevMatchFrame* F[2] = {&F1, &F2};
+    DevBuf<mmt::LocalPointDev> dp1(n[0]), dp2(n[1]);
+    DevBuf<uint8_t> pd1(32 * (size_t)n[0]), pd2(32 * (size_t)n[1]);
+    mmt::LocalPointDev* dp[2] = {dp1.p, dp2.p};
+    uint8_t* pd[2] = {pd1.p, pd2.p};
+    mmt::Sim3SearchArgs a;
+    memset(&a, 0, sizeof(a));
+    std::vector<int> hq;
+    std::vector<mmt::LocalPointDev> hp;
+    for (int d = 0; d < 2; d++) {
+      hp.assign(std::max(n[d], 1), mmt::LocalPointDev{});
+      for (int j = 0; j < n[d]; j++) {
+        memcpy(hp[j].Xw, pts[d]->Xw + 3 * (size_t)j, 12);
+        hp[j].min_dist = pts[d]->min_dist[j];
+        hp[j].max_dist = pts[d]->max_dist[j];
+        if (!skip[d][j] && !done[d][j]) hq.push_back(j);
+      }
+      if (d == 0) a.nq1 = (int)hq.size();
+      if (n[d] > 0) {
+        MMT_HIP(hipMemcpy(dp[d], hp.data(), sizeof(mmt::LocalPointDev) * (size_t)n[d],
+                          hipMemcpyHostToDevice));
+        MMT_HIP(hipMemcpyAsync(pd[d], pts[d]->desc, 32 * (size_t)n[d], hipMemcpyHostToDevice, s));
+      }
+      mmt::Sim3SearchKF& K = a.kf[d];
+      K.keys = F[d]->G.keys;
+      K.desc = F[d]->G.desc;
+      K.cell_start = F[d]->G.cell_start;
+      K.cell_idx = F[d]->G.cell_idx;
+      K.pts = dp[d];
+      K.pdesc = pd[d];
+      memcpy(K.Tcw, kf[d]->Tcw, 64);
+    }
+    a.nq = (int)hq.size();
+    // sR12 = s12 R12, sR21 = (1 / s12) R12^T, t21 = -sR21 t12 (ORBmatcher.cc:1494-1496)
+    const double inv = 1.0 / (double)s12;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) {
+        a.T[1][4 * r + c] = s12 * R12[3 * r + c];
+        a.T[0][4 * r + c] = (float)(inv * (double)R12[3 * c + r]);
+      }
+      a.T[1][4 * r + 3] = t12[r];
+    }
+    for (int r = 0; r < 3; r++) {
+      double acc = 0;
+      for (int k = 0; k < 3; k++) acc += (double)a.T[0][4 * r + k] * (double)t12[k];
+      a.T[0][4 * r + 3] = -(float)acc;
+    }
+    mmt::FuseCam& c = a.cam;
+    const mmt_config& cf = ctx->cfg;
+    c.fx = cf.fx; c.fy = cf.fy; c.cx = cf.cx; c.cy = cf.cy; c.bf = cf.bf;
+    c.W = (float)cf.width;
+    c.H = (float)cf.height;
+    c.invW = F1.G.invW;
+    c.invH = F1.G.invH;
+    c.logScale = F1.G.logScale;
+    c.th = th;
+    c.nlevels = ctx->orb.nlevels;
+    for (int l = 0; l < c.nlevels && l < mmt::kMaxLevels; l++) c.scale[l] = ctx->orb.scale[l];
+    DevBuf<int> dq(a.nq);
+    DevBuf<int2> out(a.nq);
+    std::vector<int2> ho(std::max(a.nq, 1));
+    if (a.nq > 0) {
+      MMT_HIP(hipMemcpyAsync(dq.p, hq.data(), 4 * (size_t)a.nq, hipMemcpyHostToDevice, s));
+      a.q = dq.p;
+      a.out = out.p;
+      mmt::launch_sim3_search(a, s);
+      MMT_HIP(hipMemcpyAsync(ho.data(), out.p, sizeof(int2) * (size_t)a.nq, hipMemcpyDeviceToHost,
+                             s));
+    }
+    MMT_HIP(hipStreamSynchronize(s));
+    // vnMatch1 / vnMatch2: bestDist <= TH_HIGH (:1596, :1676), then the agreement pass (:1682-1698)
+    std::vector<int32_t> vn[2] = {std::vector<int32_t>(n[0], -1), std::vector<int32_t>(n[1], -1)};
+    for (int qi = 0; qi < a.nq; qi++)
+      if (ho[qi].x >= 0 && ho[qi].y <= 100) vn[qi < a.nq1 ? 0 : 1][hq[qi]] = ho[qi].x;
+    int found = 0;
+    for (int i1 = 0; i1 < n[0]; i1++) {
+      const int idx2 = vn[0][i1];
+      match_out[i1] = -1;
+      if (idx2 >= 0 && vn[1][idx2] == i1) {
+        match_out[i1] = idx2;
+        found++;
+      }
+    }
+    *n_found = found;
+    if (cand1_out && n[0] > 0) memcpy(cand1_out, vn[0].data(), 4 * (size_t)n[0]);
+    if (cand2_out && n[1] > 0) memcpy(cand2_out, vn[1].data(), 4 * (size_t)n[1]);
+  });
+}
+
+int mmt_sim3solver_iterate(mmt_ctx* ctx, int n_solvers, const mmt_sim3_problem* problems,
+                           const int32_t* const* randi, const int32_t* n_draw_iters,
+                           int n_iterations, mmt_sim3_state* states, mmt_sim3_result* results,
+                           mmt_sim3_probe* probes) {
+  if (!ctx || (n_solvers > 0 && (!problems || !states || !results))) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    mmt::sim3solver_iterate_gpu(ctx->stream, n_solvers, problems, randi, n_draw_iters,
+                                n_iterations, states, results, probes);
   });
 }
 

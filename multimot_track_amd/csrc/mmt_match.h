@@ -206,4 +206,26 @@ struct FuseCam {
 void launch_fuse_cand(const FuseKF* kfs, const FuseQuery* q, int nq, const LocalPointDev* pool,
                       const uint8_t* pool_desc, const FuseCam& cam, int2* out, hipStream_t st);
 
+// ORBmatcher::SearchBySim3's two searches (ORBmatcher.cc:1523-1680): out[q] = (key, distance) of
+// the other keyframe's closest key in the point's window, or (-1, 256).  cam.bf and cam.invSigma2
+// are not read.
+struct Sim3SearchKF {  // a keyframe as a search target (keys, grid) and as a source (points, pose)
+  const mmt_kp* keys;
+  const uint8_t* desc;
+  const int* cell_start;
+  const int* cell_idx;
+  const LocalPointDev* pts;  // its map points in mvpMapPoints order (normal, skip unused)
+  const uint8_t* pdesc;      // their descriptors
+  float Tcw[16];
+};
+struct Sim3SearchArgs {
+  Sim3SearchKF kf[2];
+  float T[2][12];   // rows of (sR21 | t21) and of (sR12 | t12)
+  const int* q;     // point indices: nq1 of keyframe 1, then nq - nq1 of keyframe 2
+  int nq1, nq;
+  FuseCam cam;
+  int2* out;
+};
+void launch_sim3_search(const Sim3SearchArgs& a, hipStream_t st);
+
 }  // namespace mmt

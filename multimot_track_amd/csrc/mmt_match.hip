@@ -1341,6 +1341,78 @@ void launch_pool_scatter(const PoolUpdate* up, int n, LocalPointDev* pool, uint8
   MMT_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------ keyframe windows
+// The closest key of a keyframe to the descriptor dmp in the window (u, v, radius), for one wave:
+// KeyFrame::GetFeaturesInArea's cell range scanned in its order (64 positions per pass), keys at
+// level npl or one below; the key is (distance << 20 | position), so the first of equal distances
+// wins.  Returns (key index, distance), (-1, 256) for none.  This is k_fuse_cand's scan without
+// its reprojection-error gate (k_fuse_cand keeps its own copy: its code is measured as it stands).
+__device__ __forceinline__ int2 wave_window_best(const mmt_kp* keys, const uint8_t* desc,
+                                                 const int* cell_start, const int* cell_idx,
+                                                 float u, float v, float radius, int npl,
+                                                 float invW, float invH,
+                                                 const uint32_t (&dmp)[8]) {
+  const int lane = threadIdx.x & 63;
+  int2 res = make_int2(-1, 256);
+  if (!(isfinite(u) && isfinite(v))) return res;
+  const int cx0 = max(0, (int)floorf((u - 0.f - radius) * invW));
+  const int cx1 = min(kGridCols - 1, (int)ceilf((u - 0.f + radius) * invW));
+  const int cy0 = max(0, (int)floorf((v - 0.f - radius) * invH));
+  const int cy1 = min(kGridRows - 1, (int)ceilf((v - 0.f + radius) * invH));
+  if (cx0 >= kGridCols || cx1 < 0 || cy0 >= kGridRows || cy1 < 0) return res;
+  const int nseg = cx1 - cx0 + 1;
+  int sb = 0, sl = 0;
+  if (lane < nseg) {
+    const int base = (cx0 + lane) * kGridRows;
+    sb = cell_start[base + cy0];
+    sl = cell_start[base + cy1 + 1] - sb;
+  }
+  int pre = sl;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(pre, o, 64);
+    if (lane >= o) pre += y;
+  }
+  const int total = __shfl(pre, nseg - 1, 64);
+  pre -= sl;
+  uint32_t best = kNoCand;
+  int bidx = -1;
+  for (int p0 = 0; p0 < total; p0 += 64) {
+    const int pp = p0 + lane;
+    int s = 0;
+    for (int q = 1; q < nseg; q++) {
+      const int pq = __shfl(pre, q, 64);
+      if (pq <= pp) s = q;
+    }
+    const int seg_b = __shfl(sb, s, 64), seg_p = __shfl(pre, s, 64);
+    if (pp < total) {
+      const int k = cell_idx[seg_b + pp - seg_p];
+      const mmt_kp kp = keys[k];
+      bool g = fabsf(kp.x - u) < radius && fabsf(kp.y - v) < radius;
+      if (g) g = !(kp.octave < npl - 1 || kp.octave > npl);
+      if (g) {
+        const uint4* dk = reinterpret_cast<const uint4*>(desc + 32 * (size_t)k);
+        const uint4 da = dk[0], db = dk[1];
+        const int dist = __popc(da.x ^ dmp[0]) + __popc(da.y ^ dmp[1]) +
+                         __popc(da.z ^ dmp[2]) + __popc(da.w ^ dmp[3]) +
+                         __popc(db.x ^ dmp[4]) + __popc(db.y ^ dmp[5]) +
+                         __popc(db.z ^ dmp[6]) + __popc(db.w ^ dmp[7]);
+        const uint32_t key = ((uint32_t)dist << 20) | (uint32_t)pp;
+        if (key < best) {
+          best = key;
+          bidx = k;
+        }
+      }
+    }
+  }
+  const uint32_t m = wave_min_u32(best);
+  if (m != kNoCand) {
+    const int ol = __ffsll((long long)__ballot(best == m)) - 1;
+    res = make_int2(__shfl(bidx, ol, 64), (int)(m >> 20));
+  }
+  return res;
+}
+
 // ------------------------------------------------------------------------------ Fuse candidates
 // ORBmatcher::Fuse(KeyFrame*, vector<MapPoint*>, th) ORBmatcher.cc:1200-1324: the projection,
 // image / distance / viewing-angle tests, PredictScale and the best key in the window (levels
@@ -1488,6 +1560,67 @@ void launch_fuse_cand(const FuseKF* kfs, const FuseQuery* q, int nq, const Local
   if (nq <= 0) return;
   FuseArgs a{kfs, q, nq, pool, pool_desc, cam, out};
   hipLaunchKernelGGL(k_fuse_cand, dim3((nq + 3) / 4), dim3(256), 0, st, a);
+  MMT_HIP(hipGetLastError());
+}
+
+// ------------------------------------------------------------------------------ SearchBySim3
+// ORBmatcher::SearchBySim3 (ORBmatcher.cc:1477-1701), both directions in one launch: one wave per
+// query, the first nq1 being points of keyframe 1 searched among keyframe 2's keys (:1523-1600),
+// the rest points of keyframe 2 searched among keyframe 1's (:1603-1680).  The point goes into its
+// own camera with the keyframe's pose and into the other with the similarity; depth not negative,
+// IsInImage, the distance invariance on cv::norm of the camera-frame point, PredictScale, then
+// the window scan (wave_window_best).  The TH_HIGH test and the agreement pass are the host's.
+__global__ __launch_bounds__(256) void k_sim3_search(Sim3SearchArgs a) {
+  const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (qi >= a.nq) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const int d = qi < a.nq1 ? 0 : 1;  // 0: keyframe 1's point into keyframe 2
+  const int j = a.q[qi];
+  const Sim3SearchKF& own = a.kf[d];
+  const Sim3SearchKF& K = a.kf[1 - d];
+  const LocalPointDev p = own.pts[j];
+  const FuseCam& c = a.cam;
+  int2 res = make_int2(-1, 256);
+  float pOwn[3], pc[3];
+  pose_xform(own.Tcw, p.Xw, pOwn);
+  pose_xform(a.T[d], pOwn, pc);
+  bool ok = !(pc[2] < 0.0f);
+  float u = 0, v = 0, radius = 0;
+  int npl = 0;
+  if (ok) {
+    const float invz = (float)(1.0 / (double)pc[2]);
+    const float x = pc[0] * invz, y = pc[1] * invz;
+    u = c.fx * x + c.cx;
+    v = c.fy * y + c.cy;
+    ok = u >= 0.f && u < c.W && v >= 0.f && v < c.H;  // KeyFrame::IsInImage
+    if (ok) {
+      const float maxDistance = 1.2f * p.max_dist, minDistance = 0.8f * p.min_dist;
+      const double n2 = ((double)pc[0] * (double)pc[0] + (double)pc[1] * (double)pc[1]) +
+                        (double)pc[2] * (double)pc[2];
+      const float dist3D = (float)sqrt(n2);
+      ok = !(dist3D < minDistance || dist3D > maxDistance);
+      if (ok) {
+        const float ratio = p.max_dist / dist3D;  // MapPoint::PredictScale(dist3D, pKF)
+        const float ls = (float)log((double)ratio) / c.logScale;
+        npl = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
+        if (npl < 0) npl = 0;
+        else if (npl >= c.nlevels) npl = c.nlevels - 1;
+        radius = c.th * c.scale[npl];
+      }
+    }
+  }
+  if (ok) {
+    uint32_t dmp[8];
+    load_desc8(own.pdesc + 32 * (size_t)j, dmp);
+    res = wave_window_best(K.keys, K.desc, K.cell_start, K.cell_idx, u, v, radius, npl, c.invW,
+                           c.invH, dmp);
+  }
+  if (lane == 0) a.out[qi] = res;
+}
+
+void launch_sim3_search(const Sim3SearchArgs& a, hipStream_t st) {
+  if (a.nq <= 0) return;
+  hipLaunchKernelGGL(k_sim3_search, dim3((a.nq + 3) / 4), dim3(256), 0, st, a);
   MMT_HIP(hipGetLastError());
 }
 
