@@ -39,7 +39,6 @@
 
 #include <algorithm>
 #include <cfloat>
-#include <chrono>
 #include <cstdio>
 #include <climits>
 #include <cmath>
@@ -1363,8 +1362,6 @@ size_t ba2_workspace_bytes(int n_kf, int n_pt, int n_edge, int n_opt, int n_blk,
 
 
 // ------------------------------------------------------------------ host side
-static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-
 BARunner::~BARunner() {
   if (d_ws2_) (void)hipFree(d_ws2_);
   if (h_flag_) (void)hipHostFree(h_flag_);
@@ -1386,10 +1383,6 @@ void BARunner::grow(uint8_t*& d, uint8_t*& h, size_t& cap, size_t need, hipStrea
 }
 
 namespace {
-double ba_now_us() {
-  return std::chrono::duration<double, std::micro>(
-             std::chrono::steady_clock::now().time_since_epoch()).count();
-}
 // MMT_BA_PROFILE=1: host wall time of BARunner::run's phases, printed every 32 solves
 struct BAHostProf {
   bool on = getenv("MMT_BA_PROFILE") != nullptr;
@@ -1403,7 +1396,7 @@ BAHostProf g_ba_prof;
 void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* X_out,
                    uint8_t* erase, int* stats) {
   BAHostProf& hp = g_ba_prof;
-  const double tp0 = hp.on ? ba_now_us() : 0;
+  const double tp0 = hp.on ? now_us() : 0;
   const int nK = P.n_kf, nP = P.n_pt, nE = P.n_edge;
   for (int i = 0; i < nE; i++)
     if (P.e_pt[i] < 0 || P.e_pt[i] >= nP || P.e_kf[i] < 0 || P.e_kf[i] >= nK ||
@@ -1603,7 +1596,7 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
     w.pres = (double*)take(16 * (size_t)nP);
     w.spec = 0;  // k_ba2_lin linearises every trial (the trial kernel's own linearisation,
                  // k_ba2_p4<true>, measured 1,509 against 1,549 us per BA but spills)
-    const double tp1 = hp.on ? ba_now_us() : 0;
+    const double tp1 = hp.on ? now_us() : 0;
     double t_launch = 0, t_wait = 0;
     hipLaunchKernelGGL(k_ba2_init, dim3(gPp), dim3(kMkThreads), 0, st, d, w);
     MMT_HIP(hipGetLastError());
@@ -1614,7 +1607,7 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
       // g2o runs 5 + 10 iterations; on the tracker's graphs every trial is accepted, so 15 slots
       // usually finish the solve (a slot left over costs its six launches, about 30 us)
       const int batch = slots == 0 ? 15 : 4;
-      const double tl = hp.on ? ba_now_us() : 0;
+      const double tl = hp.on ? now_us() : 0;
       for (int b = 0; b < batch; b++) {
         hipLaunchKernelGGL(k_ba2_lin, dim3(gPp + gH), dim3(kPtThreads), 0, st, d, w);
         // (with no keyframe item too: its last gP workgroups build linpart)
@@ -1628,11 +1621,11 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
       MMT_HIP(hipGetLastError());
       slots += batch;
       MMT_HIP(hipMemcpyAsync(h_flag_, &w.st->done, sizeof(int), hipMemcpyDeviceToHost, st));
-      const double tw = hp.on ? ba_now_us() : 0;
+      const double tw = hp.on ? now_us() : 0;
       MMT_HIP(hipStreamSynchronize(st));
       if (hp.on) {
         t_launch += tw - tl;
-        t_wait += ba_now_us() - tw;
+        t_wait += now_us() - tw;
       }
       done = *h_flag_ != 0;
       if (!done && slots >= 160) throw DeviceError("local BA: the LM did not finish in 150 trials");
@@ -1656,7 +1649,7 @@ void BARunner::run(const BAHostProblem& P, hipStream_t st, float* T_out, float* 
   memcpy(erase, h_dn_ + o_er, (size_t)nE);
   memcpy(stats, h_dn_ + o_st, 5 * sizeof(int));
   if (hp.on) {
-    hp.t[4] += ba_now_us() - tp0;
+    hp.t[4] += now_us() - tp0;
     if (++hp.n % 32 == 0)
       fprintf(stderr, "[mmt ba profile] %ld solves, host us per solve: layout + upload %.1f, "
               "launches %.1f, waits %.1f, total %.1f; %.1f trial slots per solve\n", hp.n,

@@ -147,7 +147,6 @@ struct Stage {
 };
 
 struct MapCamH;
-void camera_centre(const float* Tcw, float* Ow);  // KeyFrame::GetCameraCenter: -Rcw^T tcw
 
 // SearchByProjection(Frame&, KeyFrame*, sAlreadyFound, th, ORBdist) over the m listed points (the
 // keyframe's map points that are neither bad nor found, in keyframe order; angle[j] = the keyframe

@@ -31,37 +31,6 @@ namespace mmt {
 namespace {
 constexpr int TH_LOW = 50, HISTO_LENGTH = 30;
 
-void cam_centre(const float* T, float* Ow) {  // -Rcw^T tcw
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)T[4 * k + 3];
-    Ow[r] = -(float)s;
-  }
-}
-void xform(const float* T, const float* x, float* y) {
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * r + k] * (double)x[k];
-    y[r] = (float)s + T[4 * r + 3];
-  }
-}
-float norm3(const float* v) {
-  double s = 0;
-  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-  return (float)std::sqrt(s);
-}
-// KeyFrame::UnprojectStereo: Rwc * ((u - cx) z / fx, (v - cy) z / fy, z) + Ow
-void unproject(const MapCamH& c, const float* T, float u, float v, float z, float* out) {
-  const float x = (u - c.cx) * z * c.invfx, y = (v - c.cy) * z * c.invfy;
-  const float xc[3] = {x, y, z};
-  float Ow[3];
-  cam_centre(T, Ow);
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)xc[k];
-    out[r] = (float)s + Ow[r];
-  }
-}
 void three_max(const std::vector<int>* histo, int& ind1, int& ind2, int& ind3) {
   int max1 = 0, max2 = 0, max3 = 0;
   for (int i = 0; i < HISTO_LENGTH; i++) {
@@ -83,16 +52,6 @@ void three_max(const std::vector<int>* histo, int& ind1, int& ind2, int& ind3) {
   } else if (max3 < 0.1f * (float)max1) {
     ind3 = -1;
   }
-}
-int hamming(const uint8_t* a, const uint8_t* b) {
-  int d = 0;
-  for (int i = 0; i < 4; i++) {
-    uint64_t x, y;
-    memcpy(&x, a + 8 * i, 8);
-    memcpy(&y, b + 8 * i, 8);
-    d += __builtin_popcountll(x ^ y);
-  }
-  return d;
 }
 // the null vector of the linear triangulation's 4x4 A (cv::SVD::compute's vt.row(3), pinned:
 // the eigenvector of A^T A for its smallest eigenvalue by cyclic Jacobi in double)
@@ -181,10 +140,7 @@ void compute_f12(const float* T1, const float* T2, const MapCamH& cam, float F[9
       F[3 * r + c] = (float)s;
     }
 }
-size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 }  // namespace
-
-void camera_centre(const float* Tcw, float* Ow) { cam_centre(Tcw, Ow); }
 
 // ------------------------------------------------------------------ glibc rand()
 GlibcRandH::GlibcRandH() {

@@ -2,6 +2,7 @@
 #pragma once
 #include <deque>
 #include <memory>
+#include <new>
 
 #include "mmt_ba.h"
 #include "mmt_bow.h"
@@ -36,3 +37,22 @@ struct mmt_ctx {
   std::deque<mmt::FrameOut> flushed;  // mmt_flush_objects records not yet handed out
   std::unique_ptr<mmt::Vocabulary> voc;  // mmt_load_vocabulary (System's ORB vocabulary)
 };
+
+// Every C-ABI entry point runs its body through this: internal exceptions become an errno-style
+// code and the context's error text; nothing exits.
+template <typename F>
+inline int guard(mmt_ctx* ctx, F&& body) {
+  try {
+    body();
+  } catch (const mmt::ArgError& e) {
+    if (ctx) ctx->err = e.msg;
+    return MMT_EINVAL;
+  } catch (const mmt::DeviceError& e) {
+    if (ctx) ctx->err = e.msg;
+    return MMT_EDEVICE;
+  } catch (const std::bad_alloc&) {
+    if (ctx) ctx->err = "host allocation failed";
+    return MMT_ENOMEM;
+  }
+  return MMT_OK;
+}

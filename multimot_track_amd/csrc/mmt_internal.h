@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <chrono>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -25,6 +26,14 @@ struct ArgError {
   std::string msg;
   explicit ArgError(std::string m) : msg(std::move(m)) {}
 };
+
+// byte offsets inside the staging blocks: the next multiple of 16
+inline size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
+// host wall clock in microseconds (the MMT_*_PROFILE timers)
+inline double now_us() {
+  return std::chrono::duration<double, std::micro>(
+             std::chrono::steady_clock::now().time_since_epoch()).count();
+}
 
 // ORB tables, computed on the host exactly like ORBextractor's ctor (ORBextractor.cc:410-470).
 struct OrbTables {

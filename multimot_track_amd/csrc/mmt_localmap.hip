@@ -22,7 +22,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -33,21 +32,6 @@
 #include "mmt_mat4.h"
 
 namespace mmt {
-
-namespace {
-size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-double now_us() {
-  return std::chrono::duration<double, std::micro>(
-             std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-void cam_centre(const float* T, float* Ow) {  // -Rcw^T tcw
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)T[4 * k + 3];
-    Ow[r] = -(float)s;
-  }
-}
-}  // namespace
 
 void MapEngine::grow_dev(uint8_t*& d, uint8_t*& h, size_t& cap, size_t need) {
   if (need <= cap && d) return;
@@ -290,9 +274,9 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
       ver.push_back(mp(h).desc_ver);
     }
   std::vector<int2> res(q.size());
-  double tb = prof_on_ ? prof_now_us() : 0;
+  double tb = prof_on_ ? now_us() : 0;
   fuse_launch(kfl, q, res.data());
-  tb = prof_on_ ? prof_now_us() : 0;
+  tb = prof_on_ ? now_us() : 0;
   for (int t = 0; t < nk; t++) {
     const int kf = kfl[t];
     for (int i = 0; i < np; i++) {
@@ -331,7 +315,7 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
 
 // ------------------------------------------------------------------ LocalMapping steps
 void MapEngine::search_in_neighbors(int kf) {  // LocalMapping::SearchInNeighbors (RGB-D: nn 10)
-  double tb = prof_on_ ? prof_now_us() : 0;
+  double tb = prof_on_ ? now_us() : 0;
   const long cur = kfs_[kf].id;
   auto best = [&](int k, size_t n) {
     const std::vector<int>& o = kfs_[k].ordered;

@@ -225,11 +225,10 @@ class MapEngine {
   // MMT_MAP_PROFILE: adds the time since t to block k and restarts t
   void blk_time(int k, double& t) {
     if (!prof_on_) return;
-    const double n = prof_now_us();
+    const double n = now_us();
     mstats_.blk_us[k] += n - t;
     t = n;
   }
-  static double prof_now_us();
   // host prefetch of map point h's record (loops over point lists walk a 100k-point map in
   // random order: one cache miss per record otherwise); MMT_NO_PREFETCH builds without it (A/B)
   void prefetch_point(int h) const {

@@ -7,7 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstdlib>
@@ -19,49 +18,12 @@
 
 namespace mmt {
 
-// ------------------------------------------------------------------ pose helpers
-// Frame::UpdatePoseMatrices / KeyFrame::SetPose: Ow = -Rcw^T tcw
-static void cam_centre(const float* T, float* Ow) {
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)T[4 * k + 3];
-    Ow[r] = -(float)s;
-  }
-}
-
-// Frame::UnprojectStereo (Frame.cc:1064-1079): Rwc * ((u - cx) z / fx, (v - cy) z / fy, z) + Ow
-static void unproject(const MapCamH& c, const float* T, float u, float v, float z, float* out) {
-  const float x = (u - c.cx) * z * c.invfx;
-  const float y = (v - c.cy) * z * c.invfy;
-  const float xc[3] = {x, y, z};
-  float Ow[3];
-  cam_centre(T, Ow);
-  for (int r = 0; r < 3; r++) {
-    double s = 0;
-    for (int k = 0; k < 3; k++) s += (double)T[4 * k + r] * (double)xc[k];
-    out[r] = (float)s + Ow[r];
-  }
-}
-
-static float norm3(const float* v) {
-  double s = 0;
-  for (int k = 0; k < 3; k++) s += (double)v[k] * (double)v[k];
-  return (float)std::sqrt(s);
-}
-
 #define MAP_PROF(k, stmt)                       \
   do {                                          \
     const double _t0 = prof_on_ ? now_us() : 0; \
     stmt;                                       \
     if (prof_on_) prof_[k] += now_us() - _t0;   \
   } while (0)
-
-static double now_us() {
-  return std::chrono::duration<double, std::micro>(
-             std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-double MapEngine::prof_now_us() { return now_us(); }
 
 MapEngine::~MapEngine() {
   if (prof_on_ && prof_n_ > 0) {
@@ -328,16 +290,6 @@ void MapEngine::compute_distinctive(int h) {  // MapPoint::ComputeDistinctiveDes
     }
   if (N == 0) return;
   const uint8_t* const* Dv = N <= kStack ? Ds : Dh.data();
-  auto hamming = [](const uint8_t* x, const uint8_t* y) {
-    int d = 0;
-    for (int w = 0; w < 4; w++) {
-      uint64_t a, b;
-      memcpy(&a, x + 8 * w, 8);
-      memcpy(&b, y + 8 * w, 8);
-      d += __builtin_popcountll(a ^ b);
-    }
-    return d;
-  };
   int dist_s[kStack * kStack], v_s[kStack];
   std::vector<int> dist_h, v_h;
   if (N > kStack) {

@@ -20,8 +20,13 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cfloat>
+#include <cmath>
+#include <cstring>
+#include <vector>
 
+#include "mmt_devbuf.h"
 #include "mmt_internal.h"
 #include "mmt_devmath.h"
 #include "mmt_pnp.h"
@@ -1377,6 +1382,167 @@ void launch_p4p_refine(PnPObject* d_obj, int row, int row_out, hipStream_t st) {
   hipLaunchKernelGGL(k_refit_beta, dim3(1, 3), dim3(64), 0, st, d_obj);
   hipLaunchKernelGGL(k_refit_rt, dim3(1), dim3(256), 0, st, d_obj);
   hipLaunchKernelGGL(k_p4p_check_rt, dim3(1), dim3(256), 0, st, d_obj, row_out);
+}
+
+// PnPsolver::iterate on the GPU (the C-ABI probe mmt_pnpsolver_iterate and the tracker's
+// Relocalization; PnPsolver.cc:119-264): SetRansacParameters' arithmetic, the hypotheses of every
+// iteration this call can run built and scored in one batch (k_pnp_hyp<4>, k_pnp_beta<4>,
+// k_p4p_check), the host replaying iterate()'s loop over their inlier counts, and every Refine()
+// it reaches on the GPU (EPnP over the best inliers + CheckInliers)
+void pnpsolver_iterate_gpu(hipStream_t s, const mmt_pnpsolver_problem* pr, const int32_t* randi,
+                           int n_draw_iters, int n_iterations, mmt_pnpsolver_state* st,
+                           float* Tcw_out, uint8_t* inliers_out, int* n_inliers, int* pose_found,
+                           int* no_more) {
+  if (pr->min_set != 4) throw ArgError("PnPsolver: min_set must be 4 (P4P)");
+  const int N = pr->n;
+  // ---- SetRansacParameters (PnPsolver.cc:119-152), the reference's int/float arithmetic
+  float eps = pr->epsilon;
+  int minInl = pr->min_inliers;
+  int nMinInliers = (int)(N * eps);
+  if (nMinInliers < minInl) nMinInliers = minInl;
+  if (nMinInliers < pr->min_set) nMinInliers = pr->min_set;
+  minInl = nMinInliers;
+  if (N > 0 && eps < (float)minInl / N) eps = (float)minInl / N;
+  int nIt;
+  if (minInl == N)
+    nIt = 1;
+  else
+    nIt = (int)ceil(log(1 - pr->probability) / log(1 - pow(eps, 3)));
+  const int maxIts = std::max(1, std::min(nIt, pr->max_iterations));
+  // ---- iterate() (PnPsolver.cc:160-264)
+  *no_more = 0;
+  *pose_found = 0;
+  *n_inliers = 0;
+  memset(inliers_out, 0, (size_t)N);
+  if (N < minInl) {
+    *no_more = 1;
+    return;
+  }
+  const int it0 = st->iterations;
+  const int K = std::max(maxIts - it0, n_iterations);  // while (its < max || cur < nIt)
+  if (K > n_draw_iters) throw ArgError("PnPsolver: randi covers fewer iterations than the call runs");
+  const int words = (N + 63) / 64;
+  // minimal sets: RandomInt draws through vAvailableIndices' swap-with-last removal
+  std::vector<int> sub(4 * (size_t)std::max(K, 1));
+  std::vector<int> avail(N);
+  for (int k = 0; k < K; k++) {
+    for (int i = 0; i < N; i++) avail[i] = i;
+    int sz = N;
+    for (int j = 0; j < 4; j++) {
+      const int r = randi[4 * (size_t)k + j];
+      if (r < 0 || r >= sz) throw ArgError("PnPsolver: randi value outside [0, n-1-j]");
+      sub[4 * (size_t)k + j] = avail[r];
+      avail[r] = avail[sz - 1];
+      sz--;
+    }
+  }
+  std::vector<float> maxErr(N);
+  for (int i = 0; i < N; i++) maxErr[i] = pr->sigma2[i] * pr->th2;
+  const int rows = K + 2;  // hypothesis masks, then the refine's input and output rows
+  DevBuf<float> p3(3 * (size_t)N + 1), merr((size_t)N + 1);
+  DevBuf<float2> p2((size_t)N + 1);
+  DevBuf<int> dn(1), dsub(sub.size()), good((size_t)K + 1), inl((size_t)N + 1), res(8);
+  DevBuf<double> hrec((size_t)kHypRec * std::max(K, 1)),
+      hout((size_t)3 * kHypOut * std::max(K, 1)), hrt(12 * (size_t)std::max(K, 1)), Rt(12);
+  DevBuf<unsigned long long> masks((size_t)rows * words + 1);
+  DevBuf<PnPObject> po(1);
+  p3.up(pr->pts3, 3 * (size_t)N, s);
+  p2.up((const float2*)pr->pts2, N, s);
+  merr.up(maxErr, s);
+  dn.up(&N, 1, s);
+  dsub.up(sub, s);
+  PnPObject o;
+  memset(&o, 0, sizeof(o));
+  o.n = dn.p;
+  o.fx = pr->fx; o.fy = pr->fy; o.cx = pr->cx; o.cy = pr->cy;
+  o.subsets = dsub.p;
+  o.pts3 = p3.p;
+  o.pts2 = p2.p;
+  o.hrec = hrec.p;
+  o.hout = hout.p;
+  o.good = good.p;
+  o.masks = masks.p;
+  o.mask_words = words;
+  o.inliers = inl.p;
+  o.result = res.p;
+  o.Rt = Rt.p;
+  o.raw_pixels = 1;
+  o.rt_raw = 1;
+  o.max_err = merr.p;
+  o.hrt = hrt.p;
+  po.up(&o, 1, s);
+  std::vector<int> h_good(std::max(K, 1));
+  if (K > 0) {
+    launch_p4p_hypotheses(po.p, K, s);
+    good.down(h_good.data(), K, s);
+  }
+  MMT_HIP(hipStreamSynchronize(s));
+  auto fetch_mask = [&](int row, uint8_t* out) {
+    std::vector<unsigned long long> w(words);
+    masks.down_now(w.data(), words, (size_t)row * words);
+    for (int i = 0; i < N; i++) out[i] = (uint8_t)((w[i >> 6] >> (i & 63)) & 1ull);
+  };
+  auto pose_to_Tcw = [](const double* Rt12, float* T) {  // cv::Mat(R, t).convertTo(CV_32F)
+    for (int r = 0; r < 4; r++)
+      for (int c = 0; c < 4; c++) T[4 * r + c] = (r == c) ? 1.f : 0.f;
+    for (int r = 0; r < 3; r++) {
+      for (int c = 0; c < 3; c++) T[4 * r + c] = (float)Rt12[3 * r + c];
+      T[4 * r + 3] = (float)Rt12[9 + r];
+    }
+  };
+  // Refine() of the current best set (st->best_mask), cached while the best set is unchanged
+  bool refined_valid = false;
+  int refined_n = 0;
+  float refined_T[16];
+  std::vector<uint8_t> refined_mask(N);
+  auto refine = [&]() {
+    if (refined_valid) return;
+    std::vector<unsigned long long> w(words, 0ull);
+    for (int i = 0; i < N; i++)
+      if (st->best_mask[i]) w[i >> 6] |= 1ull << (i & 63);
+    masks.up(w.data(), words, s, (size_t)K * words);
+    launch_p4p_refine(po.p, K, K + 1, s);
+    int r[8];
+    double rt[12];
+    res.down(r, 8, s);
+    Rt.down(rt, 12, s);
+    MMT_HIP(hipStreamSynchronize(s));
+    refined_n = r[6];
+    pose_to_Tcw(rt, refined_T);
+    fetch_mask(K + 1, refined_mask.data());
+    refined_valid = true;
+  };
+  for (int k = 0; k < K; k++) {
+    st->iterations = it0 + k + 1;
+    const int g = h_good[k];
+    if (g >= minInl) {
+      if (g > st->best_inliers) {
+        fetch_mask(k, st->best_mask);
+        st->best_inliers = g;
+        double rt[12];
+        hrt.down_now(rt, 12, 12 * (size_t)k);
+        pose_to_Tcw(rt, st->best_Tcw);
+        refined_valid = false;
+      }
+      refine();
+      if (refined_n > minInl) {  // Refine() succeeded: return the refined pose
+        *pose_found = 1;
+        *n_inliers = refined_n;
+        memcpy(inliers_out, refined_mask.data(), (size_t)N);
+        memcpy(Tcw_out, refined_T, sizeof(refined_T));
+        return;
+      }
+    }
+  }
+  if (st->iterations >= maxIts) {
+    *no_more = 1;
+    if (st->best_inliers >= minInl) {
+      *pose_found = 1;
+      *n_inliers = st->best_inliers;
+      memcpy(inliers_out, st->best_mask, (size_t)N);
+      memcpy(Tcw_out, st->best_Tcw, sizeof(st->best_Tcw));
+    }
+  }
 }
 
 void launch_pnp(PnPObject* d_objs, int nobj, int max_iters, hipStream_t st, bool gather) {

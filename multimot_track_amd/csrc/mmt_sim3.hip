@@ -20,6 +20,7 @@
 #include <cstring>
 #include <vector>
 
+#include "mmt_devbuf.h"
 #include "mmt_internal.h"
 #include "mmt_sim3.h"
 
@@ -283,17 +284,6 @@ void launch_sim3(const Sim3Args& a, hipStream_t st) {
 
 namespace {
 
-template <typename T>
-struct Sim3Buf {  // scoped device allocation
-  T* p = nullptr;
-  explicit Sim3Buf(size_t n) {
-    MMT_HIP(hipMalloc((void**)&p, (n > 0 ? n : 1) * sizeof(T)));
-  }
-  ~Sim3Buf() { (void)hipFree(p); }
-  Sim3Buf(const Sim3Buf&) = delete;
-  Sim3Buf& operator=(const Sim3Buf&) = delete;
-};
-
 // double -> int as x86 converts it: NaN and out-of-range values give INT_MIN
 int cvt_int(double v) {
   if (!(v > -2147483649.0 && v < 2147483648.0)) return INT_MIN;
@@ -389,7 +379,7 @@ void sim3solver_iterate_gpu(hipStream_t s, int n_solvers, const mmt_sim3_problem
   const int n_hyp = (int)hsol.size();
   std::vector<int> h_count(std::max(n_hyp, 1));
   std::vector<Sim3Hyp> h_hyp(std::max(n_hyp, 1));
-  Sim3Buf<uint8_t> d_flags(n_flags);
+  DevBuf<uint8_t> d_flags(n_flags);
   if (n_hyp > 0) {
     std::vector<float> X1(3 * n_pts), X2(3 * n_pts), e1(n_pts), e2(n_pts);
     for (int i = 0; i < n_solvers; i++) {
@@ -403,18 +393,17 @@ void sim3solver_iterate_gpu(hipStream_t s, int n_solvers, const mmt_sim3_problem
         e2[o + j] = sim3_max_error(pr.sigma2_2[j]);
       }
     }
-    Sim3Buf<float> dX1(3 * n_pts), dX2(3 * n_pts), de1(n_pts), de2(n_pts);
-    Sim3Buf<Sim3SolverDev> dsol(n_solvers);
-    Sim3Buf<int> dhsol(n_hyp), dsub(3 * (size_t)n_hyp), dcount(n_hyp);
-    Sim3Buf<Sim3Hyp> dhyp(n_hyp);
-    MMT_HIP(hipMemcpyAsync(dX1.p, X1.data(), 12 * n_pts, hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(dX2.p, X2.data(), 12 * n_pts, hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(de1.p, e1.data(), 4 * n_pts, hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(de2.p, e2.data(), 4 * n_pts, hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(dsol.p, sol.data(), sizeof(Sim3SolverDev) * (size_t)n_solvers,
-                           hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(dhsol.p, hsol.data(), 4 * (size_t)n_hyp, hipMemcpyHostToDevice, s));
-    MMT_HIP(hipMemcpyAsync(dsub.p, sub.data(), 12 * (size_t)n_hyp, hipMemcpyHostToDevice, s));
+    DevBuf<float> dX1(3 * n_pts), dX2(3 * n_pts), de1(n_pts), de2(n_pts);
+    DevBuf<Sim3SolverDev> dsol(n_solvers);
+    DevBuf<int> dhsol(n_hyp), dsub(3 * (size_t)n_hyp), dcount(n_hyp);
+    DevBuf<Sim3Hyp> dhyp(n_hyp);
+    dX1.up(X1, s);
+    dX2.up(X2, s);
+    de1.up(e1, s);
+    de2.up(e2, s);
+    dsol.up(sol.data(), n_solvers, s);
+    dhsol.up(hsol, s);
+    dsub.up(sub, s);
     Sim3Args a;
     a.sol = dsol.p;
     a.hsol = dhsol.p;
@@ -428,9 +417,8 @@ void sim3solver_iterate_gpu(hipStream_t s, int n_solvers, const mmt_sim3_problem
     a.flags = d_flags.p;
     a.count = dcount.p;
     launch_sim3(a, s);
-    MMT_HIP(hipMemcpyAsync(h_count.data(), dcount.p, 4 * (size_t)n_hyp, hipMemcpyDeviceToHost, s));
-    MMT_HIP(hipMemcpyAsync(h_hyp.data(), dhyp.p, sizeof(Sim3Hyp) * (size_t)n_hyp,
-                           hipMemcpyDeviceToHost, s));
+    dcount.down(h_count.data(), n_hyp, s);
+    dhyp.down(h_hyp.data(), n_hyp, s);
     MMT_HIP(hipStreamSynchronize(s));
   }
   // iterate()'s loop (Sim3Solver.cc:158-206) over the counts, hypothesis by hypothesis.  The best
@@ -453,8 +441,8 @@ void sim3solver_iterate_gpu(hipStream_t s, int n_solvers, const mmt_sim3_problem
     }
     if (last >= 0) {
       const Sim3Hyp& H = h_hyp[h0 + last];
-      MMT_HIP(hipMemcpy(st.best_mask, d_flags.p + sol[i].flag_off + (size_t)last * (size_t)pr.n,
-                        (size_t)pr.n, hipMemcpyDeviceToHost));
+      d_flags.down_now(st.best_mask, pr.n,
+                       (size_t)sol[i].flag_off + (size_t)last * (size_t)pr.n);
       hyp_to_T(H, st.best_T12);
       memcpy(st.best_R, H.R, sizeof(H.R));
       memcpy(st.best_t, H.t, sizeof(H.t));
@@ -475,9 +463,7 @@ void sim3solver_iterate_gpu(hipStream_t s, int n_solvers, const mmt_sim3_problem
         if (pb.counts) pb.counts[k] = h_count[h0 + k];
         if (pb.T12) hyp_to_T(h_hyp[h0 + k], pb.T12 + 16 * (size_t)k);
       }
-      if (pb.flags && m > 0)
-        MMT_HIP(hipMemcpy(pb.flags, d_flags.p + sol[i].flag_off, (size_t)m * (size_t)pr.n,
-                          hipMemcpyDeviceToHost));
+      if (pb.flags) d_flags.down_now(pb.flags, (size_t)m * (size_t)pr.n, sol[i].flag_off);
     }
   }
 }

@@ -30,6 +30,7 @@
 #include <string>
 #include <vector>
 
+#include "mmt_devbuf.h"
 #include "mmt_internal.h"
 #include "mmt_voctrain.h"
 
@@ -392,30 +393,6 @@ __global__ __launch_bounds__(64) void k_scatter(const VtItem* __restrict__ items
   }
 }
 
-template <typename T>
-struct DBuf {
-  T* p = nullptr;
-  size_t n = 0;
-  DBuf() = default;
-  explicit DBuf(size_t n_) { alloc(n_); }
-  DBuf(const DBuf&) = delete;
-  DBuf& operator=(const DBuf&) = delete;
-  ~DBuf() { (void)hipFree(p); }
-  void alloc(size_t n_) {
-    (void)hipFree(p);
-    p = nullptr;
-    n = std::max<size_t>(n_, 1);
-    MMT_HIP(hipMalloc((void**)&p, n * sizeof(T)));
-  }
-  void up(const std::vector<T>& h, hipStream_t st) {
-    if (!h.empty()) MMT_HIP(hipMemcpyAsync(p, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, st));
-  }
-  void down(std::vector<T>& h, size_t cnt, hipStream_t st) {
-    h.resize(cnt);
-    if (cnt) MMT_HIP(hipMemcpyAsync(h.data(), p, cnt * sizeof(T), hipMemcpyDeviceToHost, st));
-  }
-};
-
 // a node waiting for its HKmeansStep: its place in the tree under construction, its segment of
 // the permutation and its random key
 struct Pending {
@@ -458,10 +435,10 @@ void train_vocabulary(const uint8_t* desc, const int32_t* image_start, int n_ima
     return id;
   };
 
-  DBuf<uint32_t> d_desc(8 * (size_t)N), d_min(N);
-  DBuf<int> d_perm(N), d_perm2(N);
-  DBuf<uint8_t> d_assign(N);
-  MMT_HIP(hipMemcpyAsync(d_desc.p, desc, 32 * (size_t)N, hipMemcpyHostToDevice, st));
+  DevBuf<uint32_t> d_desc(8 * (size_t)N), d_min(N);
+  DevBuf<int> d_perm(N), d_perm2(N);
+  DevBuf<uint8_t> d_assign(N);
+  d_desc.up((const uint32_t*)desc, 8 * (size_t)N, st);
   std::vector<int> h_perm(N);
   for (int i = 0; i < N; i++) h_perm[i] = i;
   d_perm.up(h_perm, st);
@@ -519,12 +496,12 @@ void train_vocabulary(const uint8_t* desc, const int32_t* image_start, int n_ima
     if (nn == 0) break;
     stats.n_kmeans_nodes += nn;
 
-    DBuf<VtNode> d_nodes(nn);
-    DBuf<VtItem> d_items(ni);
-    DBuf<uint32_t> d_draws(draws.size()), d_cent((size_t)nn * k * 8), d_item_sum(ni);
-    DBuf<uint32_t> d_gcnt((size_t)nm * k * 256), d_gsize((size_t)nm * k);
-    DBuf<int> d_ncent(nn), d_multi(nm), d_flags(2 * ((size_t)nn + 1));
-    DBuf<int> d_item_cnt((size_t)ni * k), d_item_off((size_t)ni * k), d_csize((size_t)nn * k);
+    DevBuf<VtNode> d_nodes(nn);
+    DevBuf<VtItem> d_items(ni);
+    DevBuf<uint32_t> d_draws(draws.size()), d_cent((size_t)nn * k * 8), d_item_sum(ni);
+    DevBuf<uint32_t> d_gcnt((size_t)nm * k * 256), d_gsize((size_t)nm * k);
+    DevBuf<int> d_ncent(nn), d_multi(nm), d_flags(2 * ((size_t)nn + 1));
+    DevBuf<int> d_item_cnt((size_t)ni * k), d_item_off((size_t)ni * k), d_csize((size_t)nn * k);
     d_nodes.up(nodes, st);
     d_items.up(items, st);
     d_draws.up(draws, st);
@@ -589,9 +566,12 @@ void train_vocabulary(const uint8_t* desc, const int32_t* image_start, int n_ima
                        d_item_off.p, perm, perm2);
     MMT_HIP(hipGetLastError());
     std::swap(perm, perm2);
-    d_ncent.down(h_ncent, nn, st);
-    d_cent.down(h_cent, (size_t)nn * k * 8, st);
-    d_csize.down(h_csize, (size_t)nn * k, st);
+    h_ncent.resize(nn);
+    h_cent.resize((size_t)nn * k * 8);
+    h_csize.resize((size_t)nn * k);
+    d_ncent.down(h_ncent.data(), h_ncent.size(), st);
+    d_cent.down(h_cent.data(), h_cent.size(), st);
+    d_csize.down(h_csize.data(), h_csize.size(), st);
     MMT_HIP(hipMemcpyAsync(h_perm.data(), perm, 4 * (size_t)N, hipMemcpyDeviceToHost, st));
     MMT_HIP(hipStreamSynchronize(st));
 
@@ -640,11 +620,11 @@ void train_vocabulary(const uint8_t* desc, const int32_t* image_start, int n_ima
   std::vector<double> w(out.n_words(), 1.0);
   if (p.weighting == 0 || p.weighting == 2) {
     out.upload();
-    DBuf<uint32_t> d_word(N), d_node(N);
-    DBuf<double> d_w(N);
+    DevBuf<uint32_t> d_word(N), d_node(N);
+    DevBuf<double> d_w(N);
     launch_bow_transform(out.dev, (const uint8_t*)d_desc.p, N, 0, d_word.p, d_w.p, d_node.p, st);
-    std::vector<uint32_t> word;
-    d_word.down(word, N, st);
+    std::vector<uint32_t> word(N);
+    d_word.down(word.data(), word.size(), st);
     MMT_HIP(hipStreamSynchronize(st));
     std::vector<int> Ni(out.n_words(), 0), last(out.n_words(), -1);
     for (int im = 0; im < n_images; im++)

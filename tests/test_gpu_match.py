@@ -81,3 +81,32 @@ def test_search_local_points_matches_oracle(ctx, oracle_mod, name):
     assert np.array_equal(frus, ofrus)
     assert nm == onm
     assert np.array_equal(match, omatch), np.nonzero(match != omatch)[0][:10]
+
+
+def _frame32(oracle_mod):
+    c = MP.local_case(oracle_mod, "rgbd")
+    return c["kps"][:32], c["desc"][:32], c["depth"], c["tcw"]
+
+
+def test_search_local_points_no_points(ctx, oracle_mod):
+    """m = 0: the candidate kernel is not launched, every key stays unbound."""
+    kps, desc, depth, tcw = _frame32(oracle_mod)
+    f0, b0 = np.zeros((0, 3), np.float32), np.zeros(0, np.uint8)
+    nm, match, frus = ctx.search_local_points(kps, desc, depth, tcw, f0, f0, f0[:, 0], f0[:, 0],
+                                              np.zeros((0, 32), np.uint8), b0, 3.0)
+    assert nm == 0 and len(match) == 32 and np.all(match == -1) and frus.shape == (0, 6)
+
+
+def test_fuse_candidates_no_points(ctx, oracle_mod):
+    """m = 0 through the C-ABI itself: OK, and the output arrays are left as they were."""
+    import ctypes
+    import multimot_track_amd as M
+    kps, desc, depth, tcw = _frame32(oracle_mod)
+    keep = []
+    fr = ctx._match_frame(kps, desc, depth, tcw, keep)
+    P = M.MmtLocalPoints()
+    P.m = 0
+    idx, dist = np.full(4, 77, np.int32), np.full(4, 78, np.int32)
+    rc = M.lib().mmt_fuse_candidates(ctx.handle, ctypes.byref(fr), ctypes.byref(P),
+                                     ctypes.c_float(3.0), M._p(idx), M._p(dist))
+    assert rc == 0 and np.all(idx == 77) and np.all(dist == 78)

@@ -90,3 +90,12 @@ def test_pnpsolver_rejects_bad_arguments(ctx):
     with pytest.raises(M.MmtError):
         ctx.pnpsolver_iterate(p3, p2, s2, K_KITTI, np.zeros((400, 4), np.int32), 5, {},
                               (0.99, 10, 300, 5, 0.5, 5.991))
+
+
+def test_pnpsolver_fewer_points_than_min_inliers(ctx):
+    """n = 3 < min_inliers: iterate() gives up before anything is uploaded or drawn."""
+    p3, p2, s2, _ = p4p_problem(9, 3, outlier_frac=0.0)
+    gs = {}
+    g = ctx.pnpsolver_iterate(p3, p2, s2, K_KITTI, np.zeros((5, 4), np.int32), 5, gs, PARAMS)
+    assert g["no_more"] and not g["found"] and g["n_inliers"] == 0 and not g["mask"].any()
+    assert gs["iterations"] == 0

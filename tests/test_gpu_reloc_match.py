@@ -133,3 +133,31 @@ def test_probes_reject_bad_arguments(ctx, oracle_mod):
     assert sbp(points(), out=None) == EINVAL
     nodesc = ctx._match_frame(s["kps"], None, s["depth"], s["tcw"], keep)
     assert sbp(points(), frame=nodesc) == EINVAL
+
+
+def test_search_by_projection_keyframe_nothing_listed(ctx, oracle_mod):
+    """No point (m = 0) and eight points all skipped: nothing is uploaded or launched, every key
+    stays unbound and no point reaches the host rescan."""
+    c = RP.sbp_case(oracle_mod, "m5")
+    args = list(RP.sbp_args(c))
+    n = len(c["kps"])
+    for m in (0, 8):
+        args[4] = np.resize(c["Xw"], (m, 3))
+        args[5], args[6] = np.resize(c["min_dist"], m), np.resize(c["max_dist"], m)
+        args[7], args[8] = np.resize(c["pdesc"], (m, 32)), np.resize(c["angle"], m)
+        args[9] = np.ones(m, np.uint8)
+        nm, match, n_rescan = ctx.search_by_projection_keyframe(*args)
+        assert nm == 0 and n_rescan == 0 and len(match) == n and np.all(match == -1), m
+
+
+def test_search_for_triangulation_empty_keyframe1(ctx, oracle_mod):
+    """No pair, and one pair against a keyframe 1 without keys: OK, no query, no match."""
+    c = RP.sft_case(oracle_mod, "ties")
+    empty = dict(kps=np.zeros(0, RP.KP), desc=np.zeros((0, 32), np.uint8),
+                 uR=np.zeros(0, np.float32), has_mp=np.zeros(0, np.uint8),
+                 fv=(np.zeros(0, np.uint32), np.zeros(1, np.int32), np.zeros(0, np.int32)),
+                 Tcw=c["kf1"]["Tcw"])
+    nm, m, F = ctx.search_for_triangulation(empty, [])
+    assert len(nm) == 0 and m.shape == (0, 0)
+    nm, m, F = ctx.search_for_triangulation(empty, c["kf2s"][:1])
+    assert nm.tolist() == [0] and m.shape == (1, 0) and F.shape == (1, 3, 3)

@@ -189,3 +189,7 @@ def test_sim3solver_every_hypothesis(ctx, n, out, fix, seed):
     assert np.array_equal(g["hyp_flags"][keep], ref_flags[keep])
     assert np.array_equal(g["hyp_counts"], g["hyp_flags"].sum(1))
     assert np.array_equal((g["hyp_flags"] & keep).sum(1), (ref_flags & keep).sum(1))
+
+
+def test_sim3solver_no_solvers(ctx):
+    assert ctx.sim3solver_iterate([], [], 5) == []
