@@ -212,7 +212,7 @@ void MapEngine::frame_bow(MapFrameH& C, const GridFrame& G) {  // Frame::Compute
 // host work runs between them (it does not read the vectors)
 void MapEngine::kf_bow_launch(int kf) {
   const KFrame& K = kfs_[kf];
-  if (!K.hasBow) bow_launch(K.dev.desc, (int)K.keys.size(), lm_s_);
+  if (!K.hasBow) bow_launch(K.dev.g.desc, (int)K.keys.size(), lm_s_);
 }
 
 void MapEngine::kf_bow_finish(int kf) {
@@ -328,7 +328,7 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
                      (const int*)(d + o_f1)};
   const BowFeatVec b{nn2, (const uint32_t*)(d + o_n2), (const int*)(d + o_s2),
                      (const int*)(d + o_f2)};
-  launch_search_by_bow(a, K.dev.keys, K.dev.desc, d + o_ok, b, G.keys, G.desc, nF, nnratio, 1,
+  launch_search_by_bow(a, K.dev.g.keys, K.dev.g.desc, d + o_ok, b, G.keys, G.desc, nF, nnratio, 1,
                        (int*)(d + o_m), (int*)(d + o_h), (int*)(d + o_c), (const int2*)(d + o_w),
                        nw, s_);
   MMT_HIP(hipMemcpyAsync(h + o_m, d + o_m, tot - o_m, hipMemcpyDeviceToHost, s_));
@@ -788,8 +788,8 @@ void MapEngine::create_new_map_points(int kf) {
     for (size_t i = 0; i < K.keys.size(); i++) flags[i] = K.mps[i] >= 0;
     SftKeyFrame v;
     v.n = (int)K.keys.size();
-    v.d_keys = K.dev.keys;
-    v.d_desc = K.dev.desc;
+    v.d_keys = K.dev.g.keys;
+    v.d_desc = K.dev.g.desc;
     v.d_uR = K.dev.uR;
     v.fv = BowFeatVec{(int)K.fv.node.size(), K.fv.node.data(), K.fv.start.data(), K.fv.feat.data()};
     v.has_mp = flags.data();

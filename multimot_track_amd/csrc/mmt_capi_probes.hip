@@ -343,11 +343,8 @@ int mmt_fuse_candidates(mmt_ctx* ctx, const mmt_match_frame* kf, const mmt_local
     for (int j = 0; j < m; j++) hq[j] = mmt::FuseQuery{0, j};
     mmt::FuseKF K;
     memset(&K, 0, sizeof(K));
-    K.keys = F.G.keys;
-    K.desc = F.G.desc;
+    K.g = mmt::KfGrid{F.G.keys, F.G.desc, F.G.cell_start, F.G.cell_idx};
     K.uR = F.G.uR;
-    K.cell_start = F.G.cell_start;
-    K.cell_idx = F.G.cell_idx;
     K.n = kf->n;
     memcpy(K.Tcw, kf->Tcw, 64);
     mmt::cam_centre(kf->Tcw, K.Ow);  // KeyFrame::SetPose
@@ -424,10 +421,7 @@ int mmt_search_by_sim3(mmt_ctx* ctx, const mmt_match_frame* kf1,
       dp[d]->up_now(hp.data(), n[d]);  // hp ends with this turn of the loop
       pd[d]->up(pts[d]->desc, 32 * (size_t)n[d], s);
       mmt::Sim3SearchKF& K = a.kf[d];
-      K.keys = F[d]->G.keys;
-      K.desc = F[d]->G.desc;
-      K.cell_start = F[d]->G.cell_start;
-      K.cell_idx = F[d]->G.cell_idx;
+      K.g = mmt::KfGrid{F[d]->G.keys, F[d]->G.desc, F[d]->G.cell_start, F[d]->G.cell_idx};
       K.pts = dp[d]->p;
       K.pdesc = pd[d]->p;
       memcpy(K.Tcw, kf[d]->Tcw, 64);

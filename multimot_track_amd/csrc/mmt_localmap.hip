@@ -68,11 +68,11 @@ void MapEngine::kf_store_add(int kf) {
                          hipMemcpyDeviceToDevice, lm_s_));
   MMT_HIP(hipMemcpyAsync(base + o_ci, G_.cell_idx, 4 * (size_t)n, hipMemcpyDeviceToDevice, lm_s_));
   FuseKF& f = K.dev;
-  f.keys = (const mmt_kp*)base;
-  f.desc = base + o_desc;
+  f.g.keys = (const mmt_kp*)base;
+  f.g.desc = base + o_desc;
   f.uR = (const float*)(base + o_uR);
-  f.cell_start = (const int*)(base + o_cs);
-  f.cell_idx = (const int*)(base + o_ci);
+  f.g.cell_start = (const int*)(base + o_cs);
+  f.g.cell_idx = (const int*)(base + o_ci);
   f.n = n;
 }
 

@@ -184,12 +184,15 @@ void launch_pool_scatter(const PoolUpdate* up, int n, LocalPointDev* pool, uint8
 // (keyframe, point) query the best key of the keyframe (Hamming distance, first in
 // GetFeaturesInArea order) among those the reference would compare; out[q] = (key, distance), or
 // (-1, 256).  The map-changing part of Fuse is the host's.
-struct FuseKF {  // one keyframe as Fuse reads it: its Frame grid, keys, mvuRight and pose
+struct KfGrid {  // a keyframe as the target of a window search: keys, descriptors, Frame grid
   const mmt_kp* keys;
   const uint8_t* desc;
-  const float* uR;
   const int* cell_start;
   const int* cell_idx;
+};
+struct FuseKF {  // one keyframe as Fuse reads it: its keys and grid, mvuRight and pose
+  KfGrid g;
+  const float* uR;
   float Tcw[16];
   float Ow[3];
   int n;
@@ -210,10 +213,7 @@ void launch_fuse_cand(const FuseKF* kfs, const FuseQuery* q, int nq, const Local
 // the other keyframe's closest key in the point's window, or (-1, 256).  cam.bf and cam.invSigma2
 // are not read.
 struct Sim3SearchKF {  // a keyframe as a search target (keys, grid) and as a source (points, pose)
-  const mmt_kp* keys;
-  const uint8_t* desc;
-  const int* cell_start;
-  const int* cell_idx;
+  KfGrid g;
   const LocalPointDev* pts;  // its map points in mvpMapPoints order (normal, skip unused)
   const uint8_t* pdesc;      // their descriptors
   float Tcw[16];

@@ -216,24 +216,86 @@ void launch_stereo_grid(const mmt_kp* keys, const int* nkp, int cap, const float
 }
 
 // ------------------------------------------------------------------------------ windows
-// GetFeaturesInArea's cell range (Frame.cc:711-729); false when the window is empty.
-__device__ __forceinline__ bool window_cells(const GridFrame& G, float x, float y, float r,
-                                             int& cx0, int& cx1, int& cy0, int& cy1) {
+// GetFeaturesInArea's cell range (Frame.cc:711-729, KeyFrame.cc's with bounds 0); false when the
+// window is empty.
+__device__ __forceinline__ bool window_cells(float minX, float minY, float invW, float invH,
+                                             float x, float y, float r, int& cx0, int& cx1,
+                                             int& cy0, int& cy1) {
   // a non-finite centre (a map point unprojected from depth +inf) has no cells: the reference's
   // float -> int conversions are undefined there, x86 gives INT_MIN and an empty range
   if (!isfinite(x) || !isfinite(y)) return false;
-  cx0 = max(0, (int)floorf((x - G.minX - r) * G.invW));
+  cx0 = max(0, (int)floorf((x - minX - r) * invW));
   if (cx0 >= kGridCols) return false;
-  cx1 = min(kGridCols - 1, (int)ceilf((x - G.minX + r) * G.invW));
+  cx1 = min(kGridCols - 1, (int)ceilf((x - minX + r) * invW));
   if (cx1 < 0) return false;
-  cy0 = max(0, (int)floorf((y - G.minY - r) * G.invH));
+  cy0 = max(0, (int)floorf((y - minY - r) * invH));
   if (cy0 >= kGridRows) return false;
-  cy1 = min(kGridRows - 1, (int)ceilf((y - G.minY + r) * G.invH));
+  cy1 = min(kGridRows - 1, (int)ceilf((y - minY + r) * invH));
   if (cy1 < 0) return false;
   return true;
 }
 
-// Wave-cooperative candidate scan of one window (uniform arguments): enumerates the keys in
+// The keys of a cell range in GetFeaturesInArea order (x outer, y inner, key order inside a cell),
+// for one wave (uniform arguments), 64 positions per pass: visit(p, k) runs once per pass with every
+// lane active (it may ballot and shuffle), p the lane's position in that order and k its key, -1
+// past the end.  The order is what parity rests on: the first of equal distances wins.
+template <typename Visit>
+__device__ __forceinline__ void wave_window_walk(const int* cell_start, const int* cell_idx,
+                                                 int cx0, int cx1, int cy0, int cy1,
+                                                 Visit&& visit) {
+  const int lane = threadIdx.x & 63;
+  // one column segment per lane: [cell_start[ix*48+cy0], cell_start[ix*48+cy1+1])
+  const int nseg = cx1 - cx0 + 1;
+  int sb = 0, sl = 0;
+  if (lane < nseg) {
+    const int base = (cx0 + lane) * kGridRows;
+    sb = cell_start[base + cy0];
+    sl = cell_start[base + cy1 + 1] - sb;
+  }
+  int pre = sl;  // inclusive prefix of the segment lengths
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int y = __shfl_up(pre, o, 64);
+    if (lane >= o) pre += y;
+  }
+  const int total = __shfl(pre, nseg - 1, 64);
+  pre -= sl;  // exclusive
+  for (int p0 = 0; p0 < total; p0 += 64) {
+    const int p = p0 + lane;
+    int s = 0;  // this position's column segment (shuffles with every lane active)
+    for (int q = 1; q < nseg; q++) {
+      const int pq = __shfl(pre, q, 64);
+      if (pq <= p) s = q;
+    }
+    const int seg_b = __shfl(sb, s, 64), seg_p = __shfl(pre, s, 64);
+    visit(p, p < total ? cell_idx[seg_b + p - seg_p] : -1);
+  }
+}
+
+// C1: the distance of key k's descriptor (32 bytes, two 16-byte halves) to dmp
+__device__ __forceinline__ int hamming8(const uint8_t* desc, int k, const uint32_t (&dmp)[8]) {
+  const uint4* dk = reinterpret_cast<const uint4*>(desc + 32 * (size_t)k);
+  const uint4 a = dk[0], b = dk[1];
+  return __popc(a.x ^ dmp[0]) + __popc(a.y ^ dmp[1]) + __popc(a.z ^ dmp[2]) +
+         __popc(a.w ^ dmp[3]) + __popc(b.x ^ dmp[4]) + __popc(b.y ^ dmp[5]) +
+         __popc(b.z ^ dmp[6]) + __popc(b.w ^ dmp[7]);
+}
+
+// The distance invariance test in front of PredictScale, and MapPoint::PredictScale
+// (MapPoint.cc:402-417): the log in double, its quotient in float.
+__device__ __forceinline__ bool dist_in_range(float dist, float min_dist, float max_dist) {
+  return !(dist < 0.8f * min_dist || dist > 1.2f * max_dist);
+}
+__device__ __forceinline__ int predict_scale(float max_dist, float dist, float logScale,
+                                             int nlevels) {
+  const float ratio = max_dist / dist;
+  // (int)ceil of a non-finite value (a NaN point): INT_MIN on x86 -> level 0
+  const float ls = (float)log((double)ratio) / logScale;
+  const int nScale = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
+  return nScale < 0 ? 0 : min(nScale, nlevels - 1);
+}
+
+// Wave-cooperative candidate scan of one window (uniform arguments): walks the keys in
 // GetFeaturesInArea order, applies the level / area / stereo filters (and `taken`, if given),
 // computes the Hamming distance to `dmp` and keeps the K smallest (dist << 20 | order) keys.
 // On return lanes 0..K-1 hold the sorted keys (kNoCand past the end) and key indices; the
@@ -249,37 +311,12 @@ __device__ int wave_topk(const GridFrame& G, const PointWin& w, const uint32_t (
   top_key = kNoCand;
   top_idx = -1;
   int cx0, cx1, cy0, cy1;
-  if (!window_cells(G, w.x, w.y, w.r, cx0, cx1, cy0, cy1)) return 0;
+  if (!window_cells(G.minX, G.minY, G.invW, G.invH, w.x, w.y, w.r, cx0, cx1, cy0, cy1)) return 0;
   const bool checkLevels = (w.minLevel > 0) || (w.maxLevel >= 0);
-  // one column segment per lane: [cell_start[ix*48+cy0], cell_start[ix*48+cy1+1])
-  const int nseg = cx1 - cx0 + 1;
-  int sb = 0, sl = 0;
-  if (lane < nseg) {
-    const int base = (cx0 + lane) * kGridRows;
-    sb = G.cell_start[base + cy0];
-    sl = G.cell_start[base + cy1 + 1] - sb;
-  }
-  int pre = sl;  // inclusive prefix of the segment lengths
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(pre, o, 64);
-    if (lane >= o) pre += y;
-  }
-  const int total = __shfl(pre, nseg - 1, 64);
-  pre -= sl;  // exclusive
   int passed = 0;
-  for (int p0 = 0; p0 < total; p0 += 64) {
-    const int p = p0 + lane;
+  wave_window_walk(G.cell_start, G.cell_idx, cx0, cx1, cy0, cy1, [&](int p, int k) {
     uint32_t cv = kNoCand;
-    int ci = -1;
-    int s = 0;  // this position's column segment (shuffles with every lane active)
-    for (int q = 1; q < nseg; q++) {
-      const int pq = __shfl(pre, q, 64);
-      if (pq <= p) s = q;
-    }
-    const int seg_b = __shfl(sb, s, 64), seg_p = __shfl(pre, s, 64);
-    if (p < total) {
-      const int k = G.cell_idx[seg_b + p - seg_p];
+    if (k >= 0) {
       const mmt_kp kp = G.keys[k];
       bool ok = true;
       if (checkLevels) {
@@ -292,22 +329,14 @@ __device__ int wave_topk(const GridFrame& G, const PointWin& w, const uint32_t (
         const float ukr = G.uR[k];
         if (ukr > 0 && fabsf(w.ur - ukr) > w.er) ok = false;
       }
-      if (ok) {
-        const uint4* dk = reinterpret_cast<const uint4*>(G.desc + 32 * (size_t)k);
-        const uint4 a = dk[0], b = dk[1];
-        const int dist = __popc(a.x ^ dmp[0]) + __popc(a.y ^ dmp[1]) + __popc(a.z ^ dmp[2]) +
-                         __popc(a.w ^ dmp[3]) + __popc(b.x ^ dmp[4]) + __popc(b.y ^ dmp[5]) +
-                         __popc(b.z ^ dmp[6]) + __popc(b.w ^ dmp[7]);
-        cv = ((uint32_t)dist << 20) | (uint32_t)p;
-        ci = k;
-      }
+      if (ok) cv = ((uint32_t)hamming8(G.desc, k, dmp) << 20) | (uint32_t)p;
     }
     const unsigned long long vb = __ballot(cv != kNoCand);
-    if (!vb) continue;
+    if (!vb) return;
     passed += __popcll(vb);
     // merge the round into the running top-K (lanes 0..K-1)
     uint32_t a = cv, b = lane < K ? top_key : kNoCand;
-    int ai = ci, bi = top_idx;
+    int ai = k, bi = top_idx;
     uint32_t nk = kNoCand;
     int ni = -1;
     for (int r = 0; r < K; r++) {
@@ -327,7 +356,7 @@ __device__ int wave_topk(const GridFrame& G, const PointWin& w, const uint32_t (
     }
     top_key = nk;
     top_idx = ni;
-  }
+  });
   return passed;
 }
 
@@ -444,8 +473,6 @@ __global__ __launch_bounds__(256) void k_local_cand(LocalArgs a) {
       const float u = C.fx * Pc[0] * invz + C.cx;
       const float v = C.fy * Pc[1] * invz + C.cy;
       if (!(u < C.minX || u > C.maxX) && !(v < C.minY || v > C.maxY)) {
-        const float maxDistance = 1.2f * p.max_dist;
-        const float minDistance = 0.8f * p.min_dist;
         float Ow[3], PO[3];
         pose_centre(a.Tcw, Ow);
         double n2 = 0, dot = 0;
@@ -454,18 +481,12 @@ __global__ __launch_bounds__(256) void k_local_cand(LocalArgs a) {
           n2 += (double)PO[k] * (double)PO[k];
         }
         const float dist = (float)sqrt(n2);
-        if (!(dist < minDistance || dist > maxDistance)) {
+        if (dist_in_range(dist, p.min_dist, p.max_dist)) {
           for (int k = 0; k < 3; k++) dot += (double)PO[k] * (double)p.normal[k];
           const float viewCos = (float)(dot / (double)dist);
           if (!(viewCos < 0.5f)) {
-            const float ratio = p.max_dist / dist;
-            // (int)ceil of a non-finite value (a NaN point): INT_MIN on x86 -> level 0
-            const float ls = (float)log((double)ratio) / C.logScale;
-            int nScale = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
-            if (nScale < 0) nScale = 0;
-            else if (nScale >= C.nlevels) nScale = C.nlevels - 1;
             o.in_view = 1;
-            o.level = nScale;
+            o.level = predict_scale(p.max_dist, dist, C.logScale, C.nlevels);
             o.u = u;
             o.v = v;
             o.uR = u - C.bf * invz;
@@ -540,6 +561,35 @@ __device__ __forceinline__ int rot_bin(float a_last, float a_cur) {
   int bin = (int)roundf(rot * (1.0f / HISTO_LENGTH));
   if (bin == HISTO_LENGTH) bin = 0;
   return bin;
+}
+
+// ComputeThreeMaxima (ORBmatcher.cc:2236-2275) over the bin counts hist(h): the three fullest
+// bins, -1 for the second / third below a tenth of the first.  One thread.
+template <typename Hist>
+__device__ __forceinline__ void three_maxima(const Hist& hist, int* ind) {
+  int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
+  for (int h = 0; h < HISTO_LENGTH; h++) {
+    const int s = hist(h);
+    if (s > max1) {
+      max3 = max2; max2 = max1; max1 = s;
+      ind3 = ind2; ind2 = ind1; ind1 = h;
+    } else if (s > max2) {
+      max3 = max2; max2 = s;
+      ind3 = ind2; ind2 = h;
+    } else if (s > max3) {
+      max3 = s;
+      ind3 = h;
+    }
+  }
+  if (max2 < 0.1f * (float)max1) {
+    ind2 = -1;
+    ind3 = -1;
+  } else if (max3 < 0.1f * (float)max1) {
+    ind3 = -1;
+  }
+  ind[0] = ind1;
+  ind[1] = ind2;
+  ind[2] = ind3;
 }
 
 // Points bind in index order: point i takes its best (C3: best + second-best) candidate among
@@ -812,31 +862,7 @@ __global__ __launch_bounds__(kFixThreads) void k_match_fix(GreedyArgs a, int cac
   atomicAdd(&s_nm, nm);
   __syncthreads();
   if (a.mode == 0 && a.check_orientation) {
-    if (tid == 0) {
-      int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-      for (int h = 0; h < HISTO_LENGTH; h++) {
-        const int s = s_hist[h];
-        if (s > max1) {
-          max3 = max2; max2 = max1; max1 = s;
-          ind3 = ind2; ind2 = ind1; ind1 = h;
-        } else if (s > max2) {
-          max3 = max2; max2 = s;
-          ind3 = ind2; ind2 = h;
-        } else if (s > max3) {
-          max3 = s;
-          ind3 = h;
-        }
-      }
-      if (max2 < 0.1f * (float)max1) {
-        ind2 = -1;
-        ind3 = -1;
-      } else if (max3 < 0.1f * (float)max1) {
-        ind3 = -1;
-      }
-      s_ind[0] = ind1;
-      s_ind[1] = ind2;
-      s_ind[2] = ind3;
-    }
+    if (tid == 0) three_maxima([&](int h) { return s_hist[h]; }, s_ind);
     // s_owner becomes the flag of keys an event in a rejected bin clears
     for (int k = tid; k < n; k += kFixThreads) s_owner[k] = 0;
     __syncthreads();
@@ -1217,29 +1243,7 @@ __global__ __launch_bounds__(256) void k_bow_rot(BowArgs a) {
   const int tid = threadIdx.x;
   if (tid == 0) {
     s_removed = 0;
-    int max1 = 0, max2 = 0, max3 = 0, ind1 = -1, ind2 = -1, ind3 = -1;
-    for (int h = 0; h < HISTO_LENGTH; h++) {
-      const int s = a.check_orientation ? a.hist[h] : 0;
-      if (s > max1) {
-        max3 = max2; max2 = max1; max1 = s;
-        ind3 = ind2; ind2 = ind1; ind1 = h;
-      } else if (s > max2) {
-        max3 = max2; max2 = s;
-        ind3 = ind2; ind2 = h;
-      } else if (s > max3) {
-        max3 = s;
-        ind3 = h;
-      }
-    }
-    if (max2 < 0.1f * (float)max1) {
-      ind2 = -1;
-      ind3 = -1;
-    } else if (max3 < 0.1f * (float)max1) {
-      ind3 = -1;
-    }
-    s_ind[0] = ind1;
-    s_ind[1] = ind2;
-    s_ind[2] = ind3;
+    three_maxima([&](int h) { return a.check_orientation ? a.hist[h] : 0; }, s_ind);
   }
   __syncthreads();
   int removed = 0;
@@ -1345,66 +1349,36 @@ void launch_pool_scatter(const PoolUpdate* up, int n, LocalPointDev* pool, uint8
 // The closest key of a keyframe to the descriptor dmp in the window (u, v, radius), for one wave:
 // KeyFrame::GetFeaturesInArea's cell range scanned in its order (64 positions per pass), keys at
 // level npl or one below; the key is (distance << 20 | position), so the first of equal distances
-// wins.  Returns (key index, distance), (-1, 256) for none.  This is k_fuse_cand's scan without
-// its reprojection-error gate (k_fuse_cand keeps its own copy: its code is measured as it stands).
-__device__ __forceinline__ int2 wave_window_best(const mmt_kp* keys, const uint8_t* desc,
-                                                 const int* cell_start, const int* cell_idx,
-                                                 float u, float v, float radius, int npl,
-                                                 float invW, float invH,
-                                                 const uint32_t (&dmp)[8]) {
-  const int lane = threadIdx.x & 63;
+// wins.  gate(k, kp) is the caller's own test of a key inside the window and at those levels
+// (Fuse's reprojection error; none in SearchBySim3).  Returns (key index, distance), (-1, 256)
+// for none.
+struct NoGate {
+  __device__ bool operator()(int, const mmt_kp&) const { return true; }
+};
+
+template <typename Gate>
+__device__ __forceinline__ int2 wave_window_best(const KfGrid K, float u, float v, float radius,
+                                                 int npl, float invW, float invH,
+                                                 const uint32_t (&dmp)[8], const Gate& gate) {
   int2 res = make_int2(-1, 256);
-  if (!(isfinite(u) && isfinite(v))) return res;
-  const int cx0 = max(0, (int)floorf((u - 0.f - radius) * invW));
-  const int cx1 = min(kGridCols - 1, (int)ceilf((u - 0.f + radius) * invW));
-  const int cy0 = max(0, (int)floorf((v - 0.f - radius) * invH));
-  const int cy1 = min(kGridRows - 1, (int)ceilf((v - 0.f + radius) * invH));
-  if (cx0 >= kGridCols || cx1 < 0 || cy0 >= kGridRows || cy1 < 0) return res;
-  const int nseg = cx1 - cx0 + 1;
-  int sb = 0, sl = 0;
-  if (lane < nseg) {
-    const int base = (cx0 + lane) * kGridRows;
-    sb = cell_start[base + cy0];
-    sl = cell_start[base + cy1 + 1] - sb;
-  }
-  int pre = sl;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(pre, o, 64);
-    if (lane >= o) pre += y;
-  }
-  const int total = __shfl(pre, nseg - 1, 64);
-  pre -= sl;
+  int cx0, cx1, cy0, cy1;
+  if (!window_cells(0.f, 0.f, invW, invH, u, v, radius, cx0, cx1, cy0, cy1)) return res;
   uint32_t best = kNoCand;
   int bidx = -1;
-  for (int p0 = 0; p0 < total; p0 += 64) {
-    const int pp = p0 + lane;
-    int s = 0;
-    for (int q = 1; q < nseg; q++) {
-      const int pq = __shfl(pre, q, 64);
-      if (pq <= pp) s = q;
-    }
-    const int seg_b = __shfl(sb, s, 64), seg_p = __shfl(pre, s, 64);
-    if (pp < total) {
-      const int k = cell_idx[seg_b + pp - seg_p];
-      const mmt_kp kp = keys[k];
-      bool g = fabsf(kp.x - u) < radius && fabsf(kp.y - v) < radius;
-      if (g) g = !(kp.octave < npl - 1 || kp.octave > npl);
-      if (g) {
-        const uint4* dk = reinterpret_cast<const uint4*>(desc + 32 * (size_t)k);
-        const uint4 da = dk[0], db = dk[1];
-        const int dist = __popc(da.x ^ dmp[0]) + __popc(da.y ^ dmp[1]) +
-                         __popc(da.z ^ dmp[2]) + __popc(da.w ^ dmp[3]) +
-                         __popc(db.x ^ dmp[4]) + __popc(db.y ^ dmp[5]) +
-                         __popc(db.z ^ dmp[6]) + __popc(db.w ^ dmp[7]);
-        const uint32_t key = ((uint32_t)dist << 20) | (uint32_t)pp;
-        if (key < best) {
-          best = key;
-          bidx = k;
-        }
+  wave_window_walk(K.cell_start, K.cell_idx, cx0, cx1, cy0, cy1, [&](int p, int k) {
+    if (k < 0) return;
+    const mmt_kp kp = K.keys[k];
+    bool g = fabsf(kp.x - u) < radius && fabsf(kp.y - v) < radius;
+    if (g) g = !(kp.octave < npl - 1 || kp.octave > npl);
+    if (g) g = gate(k, kp);
+    if (g) {
+      const uint32_t key = ((uint32_t)hamming8(K.desc, k, dmp) << 20) | (uint32_t)p;
+      if (key < best) {
+        best = key;
+        bidx = k;
       }
     }
-  }
+  });
   const uint32_t m = wave_min_u32(best);
   if (m != kNoCand) {
     const int ol = __ffsll((long long)__ballot(best == m)) - 1;
@@ -1452,7 +1426,6 @@ __global__ __launch_bounds__(256) void k_fuse_cand(FuseArgs a) {
     ok = u >= 0.f && u < c.W && v >= 0.f && v < c.H;  // KeyFrame::IsInImage
     if (ok) {
       ur = u - c.bf * invz;
-      const float maxDistance = 1.2f * p.max_dist, minDistance = 0.8f * p.min_dist;
       float PO[3];
       double n2 = 0;
       for (int k = 0; k < 3; k++) {
@@ -1460,97 +1433,36 @@ __global__ __launch_bounds__(256) void k_fuse_cand(FuseArgs a) {
         n2 += (double)PO[k] * (double)PO[k];
       }
       const float dist3D = (float)sqrt(n2);
-      ok = !(dist3D < minDistance || dist3D > maxDistance);
+      ok = dist_in_range(dist3D, p.min_dist, p.max_dist);
       if (ok) {
         double dot = 0;
         for (int k = 0; k < 3; k++) dot += (double)PO[k] * (double)p.normal[k];
         ok = !(dot < 0.5 * (double)dist3D);  // viewing angle under 60 degrees
       }
       if (ok) {
-        const float ratio = p.max_dist / dist3D;  // MapPoint::PredictScale(dist3D, pKF)
-        const float ls = (float)log((double)ratio) / c.logScale;
-        npl = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
-        if (npl < 0) npl = 0;
-        else if (npl >= c.nlevels) npl = c.nlevels - 1;
+        npl = predict_scale(p.max_dist, dist3D, c.logScale, c.nlevels);
         radius = c.th * c.scale[npl];
       }
     }
   }
-  int cx0 = 0, cx1 = -1, cy0 = 0, cy1 = -1;
-  if (ok && isfinite(u) && isfinite(v)) {  // KeyFrame::GetFeaturesInArea's cell range
-    cx0 = max(0, (int)floorf((u - 0.f - radius) * c.invW));
-    cx1 = min(kGridCols - 1, (int)ceilf((u - 0.f + radius) * c.invW));
-    cy0 = max(0, (int)floorf((v - 0.f - radius) * c.invH));
-    cy1 = min(kGridRows - 1, (int)ceilf((v - 0.f + radius) * c.invH));
-    if (cx0 >= kGridCols || cx1 < 0 || cy0 >= kGridRows || cy1 < 0) ok = false;
-  } else {
-    ok = false;
-  }
   if (ok) {
     uint32_t dmp[8];
     load_desc8(a.pool_desc + 32 * (size_t)Q.h, dmp);
-    const int nseg = cx1 - cx0 + 1;
-    int sb = 0, sl = 0;
-    if (lane < nseg) {
-      const int base = (cx0 + lane) * kGridRows;
-      sb = K.cell_start[base + cy0];
-      sl = K.cell_start[base + cy1 + 1] - sb;
-    }
-    int pre = sl;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int y = __shfl_up(pre, o, 64);
-      if (lane >= o) pre += y;
-    }
-    const int total = __shfl(pre, nseg - 1, 64);
-    pre -= sl;
-    uint32_t best = kNoCand;
-    int bidx = -1;
-    for (int p0 = 0; p0 < total; p0 += 64) {
-      const int pp = p0 + lane;
-      int s = 0;
-      for (int q = 1; q < nseg; q++) {
-        const int pq = __shfl(pre, q, 64);
-        if (pq <= pp) s = q;
+    // the reprojection error of the key: stereo (chi2 7.8) where it has a right coordinate
+    const float* kuR = K.uR;
+    const float* invSigma2 = c.invSigma2;
+    const auto gate = [=](int k, const mmt_kp& kp) {
+      const float ex = u - kp.x, ey = v - kp.y;
+      const float kr = kuR[k];
+      if (kr >= 0) {
+        const float er = ur - kr;
+        const float e2 = ex * ex + ey * ey + er * er;
+        return !((double)(e2 * invSigma2[kp.octave]) > 7.8);
       }
-      const int seg_b = __shfl(sb, s, 64), seg_p = __shfl(pre, s, 64);
-      if (pp < total) {
-        const int k = K.cell_idx[seg_b + pp - seg_p];
-        const mmt_kp kp = K.keys[k];
-        bool g = fabsf(kp.x - u) < radius && fabsf(kp.y - v) < radius;
-        if (g) g = !(kp.octave < npl - 1 || kp.octave > npl);
-        if (g) {
-          const float ex = u - kp.x, ey = v - kp.y;
-          const float kr = K.uR[k];
-          if (kr >= 0) {
-            const float er = ur - kr;
-            const float e2 = ex * ex + ey * ey + er * er;
-            g = !((double)(e2 * c.invSigma2[kp.octave]) > 7.8);
-          } else {
-            const float e2 = ex * ex + ey * ey;
-            g = !((double)(e2 * c.invSigma2[kp.octave]) > 5.99);
-          }
-        }
-        if (g) {
-          const uint4* dk = reinterpret_cast<const uint4*>(K.desc + 32 * (size_t)k);
-          const uint4 da = dk[0], db = dk[1];
-          const int dist = __popc(da.x ^ dmp[0]) + __popc(da.y ^ dmp[1]) +
-                           __popc(da.z ^ dmp[2]) + __popc(da.w ^ dmp[3]) +
-                           __popc(db.x ^ dmp[4]) + __popc(db.y ^ dmp[5]) +
-                           __popc(db.z ^ dmp[6]) + __popc(db.w ^ dmp[7]);
-          const uint32_t key = ((uint32_t)dist << 20) | (uint32_t)pp;
-          if (key < best) {
-            best = key;
-            bidx = k;
-          }
-        }
-      }
-    }
-    const uint32_t m = wave_min_u32(best);
-    if (m != kNoCand) {
-      const int ol = __ffsll((long long)__ballot(best == m)) - 1;
-      res = make_int2(__shfl(bidx, ol, 64), (int)(m >> 20));
-    }
+      const float e2 = ex * ex + ey * ey;
+      return !((double)(e2 * invSigma2[kp.octave]) > 5.99);
+    };
+    res = wave_window_best(K.g, u, v, radius, npl, c.invW, c.invH, dmp, gate);
   }
   if (lane == 0) a.out[qi] = res;
 }
@@ -1594,17 +1506,12 @@ __global__ __launch_bounds__(256) void k_sim3_search(Sim3SearchArgs a) {
     v = c.fy * y + c.cy;
     ok = u >= 0.f && u < c.W && v >= 0.f && v < c.H;  // KeyFrame::IsInImage
     if (ok) {
-      const float maxDistance = 1.2f * p.max_dist, minDistance = 0.8f * p.min_dist;
       const double n2 = ((double)pc[0] * (double)pc[0] + (double)pc[1] * (double)pc[1]) +
                         (double)pc[2] * (double)pc[2];
       const float dist3D = (float)sqrt(n2);
-      ok = !(dist3D < minDistance || dist3D > maxDistance);
+      ok = dist_in_range(dist3D, p.min_dist, p.max_dist);
       if (ok) {
-        const float ratio = p.max_dist / dist3D;  // MapPoint::PredictScale(dist3D, pKF)
-        const float ls = (float)log((double)ratio) / c.logScale;
-        npl = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
-        if (npl < 0) npl = 0;
-        else if (npl >= c.nlevels) npl = c.nlevels - 1;
+        npl = predict_scale(p.max_dist, dist3D, c.logScale, c.nlevels);
         radius = c.th * c.scale[npl];
       }
     }
@@ -1612,8 +1519,7 @@ __global__ __launch_bounds__(256) void k_sim3_search(Sim3SearchArgs a) {
   if (ok) {
     uint32_t dmp[8];
     load_desc8(own.pdesc + 32 * (size_t)j, dmp);
-    res = wave_window_best(K.keys, K.desc, K.cell_start, K.cell_idx, u, v, radius, npl, c.invW,
-                           c.invH, dmp);
+    res = wave_window_best(K.g, u, v, radius, npl, c.invW, c.invH, dmp, NoGate());
   }
   if (lane == 0) a.out[qi] = res;
 }
@@ -1657,15 +1563,8 @@ __global__ __launch_bounds__(256) void k_sbp_kf(SbpKfArgs a) {
       n2 += (double)d * (double)d;
     }
     const float dist3D = (float)sqrt(n2);
-    const float maxDistance = 1.2f * p.max_dist, minDistance = 0.8f * p.min_dist;
-    ok = !(dist3D < minDistance || dist3D > maxDistance);
-    if (ok) {  // MapPoint::PredictScale(dist3D, &CurrentFrame)
-      const float ratio = p.max_dist / dist3D;
-      const float ls = (float)log((double)ratio) / C.logScale;
-      npl = isfinite(ls) ? (int)ceilf(ls) : INT_MIN;
-      if (npl < 0) npl = 0;
-      else if (npl >= C.nlevels) npl = C.nlevels - 1;
-    }
+    ok = dist_in_range(dist3D, p.min_dist, p.max_dist);
+    if (ok) npl = predict_scale(p.max_dist, dist3D, C.logScale, C.nlevels);
   }
   if (!ok) {
     if (lane < kSbpKfCand) {
