@@ -13,7 +13,7 @@ INV_SIGMA2 = (1.0 / (1.2 ** (2 * np.arange(8)))).astype(np.float32)
 
 def ba_problem(seed, n_kf=6, n_fixed=2, n_pt=800, obs_per_pt=(1, 4), mono_frac=0.15,
                pix_noise=0.5, pose_noise=0.01, pt_noise=0.05, outlier_frac=0.03, kf0_local=True,
-               K=K_KITTI, w=1242, h=375):
+               K=K_KITTI, w=1242, h=375, bf=BF):
     """n_kf keyframe vertices (the first n_kf - n_fixed local, the rest fixed cameras; with
     kf0_local the first local one is keyframe 0, itself fixed) and n_pt points, each seen by a
     random run of consecutive keyframes.  Returns (problem dict, true poses, true points)."""
@@ -51,7 +51,7 @@ def ba_problem(seed, n_kf=6, n_fixed=2, n_pt=800, obs_per_pt=(1, 4), mono_frac=0
             if rng.uniform() < outlier_frac:
                 u += rng.uniform(-25, 25)
                 v += rng.uniform(-25, 25)
-            ur = -1.0 if rng.uniform() < mono_frac else u - BF / p[2] + rng.normal(scale=pix_noise)
+            ur = -1.0 if rng.uniform() < mono_frac else u - bf / p[2] + rng.normal(scale=pix_noise)
             octave = rng.integers(0, 8)
             pts.append(j)
             kfs.append(k)

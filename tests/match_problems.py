@@ -48,7 +48,7 @@ def poses(O, n=3):
     return _CACHE[key]
 
 
-def map_points(kps, desc, depth, Tcw, rng, flip_bits=8, max_depth=40.0):
+def map_points(kps, desc, depth, Tcw, rng, flip_bits=8, max_depth=40.0, K=K):
     """Back-project keys with valid depth to world points (Frame::UnprojectStereo) and give them
     descriptors, normals and distance bounds.  Returns (Xw, mp_desc, valid, normal, dmin, dmax)."""
     n = len(kps)
@@ -73,7 +73,7 @@ def map_points(kps, desc, depth, Tcw, rng, flip_bits=8, max_depth=40.0):
     return Xw, md, valid, normal, dmin, dmax
 
 
-def sbp_case(O, name, seed=0):
+def sbp_case(O, name, seed=0, K=K):
     """Inputs of SearchByProjection(Frame&, const Frame&, th, bMono) for a named case."""
     rng = np.random.default_rng(seed)
     T = poses(O)
@@ -106,7 +106,7 @@ def sbp_case(O, name, seed=0):
         raise KeyError(name)
     lk, ld, ldep = frame(O, li)
     ck, cd, cdep = frame(O, ci)
-    Xw, md, valid, *_ = map_points(lk, ld, ldep, Tl, rng)
+    Xw, md, valid, *_ = map_points(lk, ld, ldep, Tl, rng, K=K)
     active = valid & (rng.random(len(lk)) > 0.1)
     if dup > 1:
         sel = np.nonzero(active)[0][::7][:60]
@@ -131,7 +131,7 @@ def sbp_case(O, name, seed=0):
                 check_orientation=check, obs=obs)
 
 
-def local_case(O, name, seed=0):
+def local_case(O, name, seed=0, K=K):
     """Inputs of SearchLocalPoints / SearchByProjection(Frame&, vector<MapPoint*>, th)."""
     rng = np.random.default_rng(seed)
     T = poses(O)
@@ -152,7 +152,7 @@ def local_case(O, name, seed=0):
     parts = []
     for si in src:
         k, d, dep = frame(O, si)
-        Xw, md, valid, normal, dmin, dmax = map_points(k, d, dep, T[si], rng)
+        Xw, md, valid, normal, dmin, dmax = map_points(k, d, dep, T[si], rng, K=K)
         sel = np.nonzero(valid)[0]
         parts.append((Xw[sel], md[sel], normal[sel], dmin[sel], dmax[sel]))
     Xw, md, normal, dmin, dmax = [np.concatenate(x) for x in zip(*parts)]

@@ -186,14 +186,14 @@ class _Sbp:
             th=self.th, orb_dist=self.orb, bound=np.array(self.kbound, np.uint8), tags=self.tags)
 
 
-def _sbp_round(O, which, stride):
+def _sbp_round(O, which, stride, K=K):
     """The reference's two calls on kitti_sample: frame 1 at the oracle's pose against points
     back-projected from frame 0; ~20 % of the keys bound, ~10 % of the points in sAlreadyFound."""
     rng = np.random.default_rng(20 + which)
     T = MP.poses(O)
     (k0, d0, dep0), (k1, d1, dep1) = [(k[:2000], d[:2000], dep) for k, d, dep in
                                       (MP.frame(O, 0), MP.frame(O, 1))]
-    Xw, md, valid, _, dmin, dmax = MP.map_points(k0, d0, dep0, T[0], rng)
+    Xw, md, valid, _, dmin, dmax = MP.map_points(k0, d0, dep0, T[0], rng, K=K)
     skip = (~valid) | (rng.random(len(k0)) < 0.1)
     if stride > 1:
         skip |= (np.arange(len(k0)) % stride) != 0
@@ -372,13 +372,15 @@ SBP_CASES = ["round1", "round2", "crowded_a", "crowded_b", "degenerate", "orbdis
 SBP_KITTI = ("round1", "round2")
 
 
-def sbp_case(O, name, stride=1):
+def sbp_case(O, name, stride=1, K=K):
     """Inputs of one named SearchByProjection(F, KF) case (cached: callers must not write to
-    them).  stride > 1 keeps every stride-th point of the kitti cases."""
-    key = ("sbp", name, stride)
+    them).  stride > 1 keeps every stride-th point of the kitti cases; K is the camera the kitti
+    cases' points are back-projected with (the hand-built cases are KITTI's)."""
+    assert K == MP.K or name in SBP_KITTI, name
+    key = ("sbp", name, stride, K)
     if key not in _CACHE:
         if name in SBP_KITTI:
-            c = _sbp_round(O, SBP_KITTI.index(name), stride)
+            c = _sbp_round(O, SBP_KITTI.index(name), stride, K)
         elif name.startswith("crowded_"):
             c = _sbp_crowded(name[-1])
         elif name == "degenerate":
@@ -431,7 +433,7 @@ def epipolar_line(F, x1, y1):
             x1 * F[0, 2] + y1 * F[1, 2] + F[2, 2])
 
 
-def epipole(T1, T2):
+def epipole(T1, T2, K=K):
     """Projection of keyframe 1's centre into keyframe 2 (float64)."""
     T1 = T1.astype(np.float64)
     T2 = T2.astype(np.float64)
@@ -503,7 +505,7 @@ class _Sft:
         return dict(kf1=out[0], kf2s=[out[1]], tags=self.tags)
 
 
-def _sft_kitti(O, stride):
+def _sft_kitti(O, stride, K=K, BF=BF):
     """kitti_sample frame 0 against frames 1 and 2 in one call: poses from the oracle tracker,
     mvuRight from the oracle's frame grid, FeatureVectors from the test vocabulary; about half of
     the keys hold a MapPoint and 30 % of the rest are monocular (uR = -1)."""
@@ -518,7 +520,7 @@ def _sft_kitti(O, stride):
         has = rng.random(len(k)) < 0.5
         uR[(~has) & (rng.random(len(k)) < 0.3)] = -1
         # the keys around the focus of expansion: free and monocular, so the epipole test acts
-        ex, ey = epipole(T[0], T[max(i, 1)])
+        ex, ey = epipole(T[0], T[max(i, 1)], K)
         near = np.hypot(k["x"] - ex, k["y"] - ey) < 30
         has[near] = False
         uR[near] = -1
@@ -639,14 +641,16 @@ SFT_CASES = ["kitti", "th_low_edge", "ties", "epipole", "den_zero", "one_node", 
              "nq_257", "three_pairs", "empty_kf1", "empty_kf2"]
 
 
-def sft_case(O, name, stride=1):
+def sft_case(O, name, stride=1, K=K, BF=BF):
     """Inputs of one named SearchForTriangulation case (cached: callers must not write to them):
-    dict(kf1, kf2s, tags).  stride > 1 keeps every stride-th query feature of the kitti case."""
-    key = ("sft", name, stride)
+    dict(kf1, kf2s, tags).  stride > 1 keeps every stride-th query feature of the kitti case; K, BF
+    are the camera of the kitti case (the hand-built cases are KITTI's)."""
+    assert (K, BF) == (MP.K, MP.BF) or name == "kitti", name
+    key = ("sft", name, stride, K, BF)
     if key in _CACHE:
         return _CACHE[key]
     if name == "kitti":
-        c = _sft_kitti(O, stride)
+        c = _sft_kitti(O, stride, K, BF)
     elif name == "th_low_edge":
         c = _sft_th_low_edge()
     elif name == "ties":

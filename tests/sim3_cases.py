@@ -42,27 +42,28 @@ def true_sim3(rng, fix_scale):
     return s, R, t
 
 
-def solver_problem(seed, n, outlier_frac, noise, fix_scale, min_inliers=20):
+def solver_problem(seed, n, outlier_frac, noise, fix_scale, min_inliers=20, K1=K_KITTI,
+                   K2=K_KITTI):
     """A Sim3Solver problem dict (Context.sim3solver_iterate's) with its truth: s, R, t and the
     inlier flags.  noise: standard deviation of the 3D noise in pixels at the point's depth."""
     rng = np.random.default_rng(seed)
     s, R, t = true_sim3(rng, fix_scale)
-    X1 = points_ahead(rng, n)
+    X1 = points_ahead(rng, n, K1)
     X2 = ((X1 - t) @ R) / s  # R^T (X1 - t) / s
-    fx = K_KITTI[0]
+    fx = K1[0]
     X1n = X1 + rng.normal(size=(n, 3)) * (noise * X1[:, 2:3] / fx)
     X2n = X2 + rng.normal(size=(n, 3)) * (noise * X2[:, 2:3] / fx)
     inl = np.ones(n, bool)
     n_out = int(round(outlier_frac * n))
     if n_out:
         bad = rng.choice(n, n_out, replace=False)
-        X2n[bad] = points_ahead(rng, n_out)
+        X2n[bad] = points_ahead(rng, n_out, K2)
         inl[bad] = False
     _, sigma2 = orb_scales()
     o1 = rng.integers(0, NLEVELS, n)
     o2 = np.clip(o1 + rng.integers(-1, 2, n), 0, NLEVELS - 1)
     return dict(X1=X1n.astype(f32), X2=X2n.astype(f32), sigma2_1=sigma2[o1], sigma2_2=sigma2[o2],
-                K1=K_KITTI, K2=K_KITTI, fix_scale=fix_scale, probability=0.99,
+                K1=K1, K2=K2, fix_scale=fix_scale, probability=0.99,
                 min_inliers=min_inliers, max_iterations=300,
                 truth=dict(s=s, R=R, t=t, inliers=inl))
 
@@ -88,7 +89,7 @@ def _project(p, K=K_KITTI):
     return np.stack([fx * p[:, 0] / p[:, 2] + cx, fy * p[:, 1] / p[:, 2] + cy], 1)
 
 
-def keyframe_pair(seed, n_mutual, n_only=40, n_empty=40, s12=1.0, pix_noise=0.3):
+def keyframe_pair(seed, n_mutual, n_only=40, n_empty=40, s12=1.0, pix_noise=0.3, K=K_KITTI):
     """Two keyframes that see n_mutual common points under a known similarity (p1 = s12 R12 p2 +
     t12 between the camera frames), each with n_only points of its own and n_empty keys without a
     point.  The common points hold slots 0..n_mutual-1 of both keyframes, in a different order in
@@ -101,11 +102,11 @@ def keyframe_pair(seed, n_mutual, n_only=40, n_empty=40, s12=1.0, pix_noise=0.3)
     log12 = np.log(1.2)
     P1, P2, O1, O2 = [], [], [], []
     while len(P1) < n_mutual:
-        p1 = points_ahead(rng, 1)[0]
+        p1 = points_ahead(rng, 1, K)[0]
         p2 = (R12.T @ (p1 - t12)) / s12
         if p2[2] < 4.0:
             continue
-        uv = _project(p2[None])[0]
+        uv = _project(p2[None], K)[0]
         if not (40 <= uv[0] < W - 40 and 40 <= uv[1] < H - 40):
             continue
         delta = np.log(np.linalg.norm(p1) / np.linalg.norm(p2)) / log12
@@ -131,10 +132,10 @@ def keyframe_pair(seed, n_mutual, n_only=40, n_empty=40, s12=1.0, pix_noise=0.3)
     kfs = []
     for side, (P, O) in enumerate(((P1, O1), (P2, O2))):
         n = n_mutual + n_only + n_empty
-        own = points_ahead(rng, n_only)
-        pc = np.concatenate([P, own, points_ahead(rng, n_empty)])
+        own = points_ahead(rng, n_only, K)
+        pc = np.concatenate([P, own, points_ahead(rng, n_empty, K)])
         octs = np.concatenate([np.array(O), rng.integers(1, 7, n_only + n_empty)])
-        uv = _project(pc) + rng.normal(size=(n, 2)) * pix_noise
+        uv = _project(pc, K) + rng.normal(size=(n, 2)) * pix_noise
         uv[:, 0] = np.clip(uv[:, 0], 1, W - 2)
         uv[:, 1] = np.clip(uv[:, 1], 1, H - 2)
         slot = np.arange(n)
