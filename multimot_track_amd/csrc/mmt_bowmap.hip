@@ -921,8 +921,8 @@ void MapEngine::create_new_map_points(int kf) {
       const int hnew = new_point_kf(x3D, kf);  // MapPoint(x3D, mpCurrentKeyFrame, mpMap)
       add_observation(hnew, kf, idx1);
       add_observation(hnew, k2, idx2);
-      kfs_[kf].mps[idx1] = hnew;
-      kfs_[k2].mps[idx2] = hnew;
+      kf_set_mp(kf, idx1, hnew);
+      kf_set_mp(k2, idx2, hnew);
       compute_distinctive(hnew);
       update_normal_depth(hnew);
       recent_.push_back(hnew);

@@ -113,10 +113,10 @@ void MapEngine::replace(int h, int by) {  // MapPoint::Replace (this = h, pMP = 
   mark_dirty(h);
   for (const auto& kv : obs) {
     if (mp(by).obs_index(kv.first) < 0) {
-      kfs_[kv.first].mps[kv.second] = by;  // ReplaceMapPointMatch
+      kf_set_mp(kv.first, kv.second, by);  // ReplaceMapPointMatch
       add_observation(by, kv.first, kv.second);
     } else {
-      kfs_[kv.first].mps[kv.second] = -1;  // EraseMapPointMatch(idx)
+      kf_set_mp(kv.first, kv.second, -1);  // EraseMapPointMatch(idx)
     }
   }
   MPoint& q = mp(by);
@@ -174,6 +174,7 @@ void MapEngine::kf_set_bad(int kf) {  // KeyFrame::SetBadFlag (mbNotErase is nev
     kfs_[K.parent].children.erase(kf);
   }
   K.bad = true;
+  struct_epoch_++;  // the bad flag, ordered, and the spanning tree's parents and children above
   kfdb_erase(kf);  // mpKeyFrameDB->erase(this) (KeyFrame.cc:544)
 }
 
@@ -248,7 +249,7 @@ void MapEngine::fuse_apply(int kf, int h, int bestIdx, int bestDist) {
     }
   } else {
     add_observation(h, kf, bestIdx);
-    K.mps[bestIdx] = h;
+    kf_set_mp(kf, bestIdx, h);
   }
   mstats_.n_fused++;
 }
@@ -459,7 +460,7 @@ void MapEngine::local_bundle_adjustment(int kf) {  // Optimizer::LocalBundleAdju
       if (stereo != (pass == 1) || !er[i]) continue;
       const int h = lpts[e_pt[i]], k = e_kfid[i];
       const int idx = mp(h).obs_index(k);  // KeyFrame::EraseMapPointMatch(pMP)
-      if (idx >= 0) kfs_[k].mps[idx] = -1;
+      if (idx >= 0) kf_set_mp(k, idx, -1);
       erase_observation(h, k);
       mstats_.n_ba_erased++;
     }

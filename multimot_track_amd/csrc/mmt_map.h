@@ -269,7 +269,48 @@ class MapEngine {
   void spec_discard();
   template <class Marked, class Mark>
   void expand_local_kfs(std::vector<int>& kfl, Marked marked, Mark mark);
-  void collect_local_points(const std::vector<int>& kfl, std::vector<int>& out);
+  // out: the local points of the keyframes kfl; gen: the generation of the list out holds, in
+  // and out (a list with an equal generation is equal element for element)
+  void collect_local_points(const std::vector<int>& kfl, std::vector<int>& out, long& gen);
+  void walk_local_points(const std::vector<int>& kfl, std::vector<int>& out);
+  // The structure epoch: bumped by every edit of what walk_local_points and expand_local_kfs
+  // read, so a point list built at this epoch from an equal keyframe list is still the list a
+  // walk would build.  The mutators (a missed one is the one way the cache below can be wrong):
+  //  * KFrame::mps entries of a stored keyframe: kf_set_mp, the only writer (set_bad, replace,
+  //    fuse_apply, local_bundle_adjustment's erasures, initialize, create_new_keyframe,
+  //    create_new_map_points); new_keyframe, which stores the frame's table whole;
+  //  * a point's bad flag: mark_bad, the only writer (set_bad, replace);
+  //  * a keyframe's bad flag, parent and children: kf_set_bad, update_connections;
+  //  * KFrame::ordered: update_best_covisibles (add_connection, erase_connection),
+  //    update_connections, kf_set_bad;
+  //  * reset and initialize.
+  // Temporary (VO) points (handles >= kTemp) are never in a keyframe and need no epoch.
+  long struct_epoch_ = 0;
+  void kf_set_mp(int kf, int idx, int h) {
+    kfs_[kf].mps[idx] = h;
+    struct_epoch_++;
+  }
+  // The keyframe list and point list of the last walks (copies: commit_local_map swaps the
+  // vectors the callers hold), each list's generation and the epoch they were built at (one for
+  // all: a structure edit drops every kept list).  MMT_LOCALMAP_CACHE:
+  // 1 (default) a call with an equal keyframe list at an unchanged epoch takes the cached points;
+  // 0 walks every time (A/B); 2 also walks on every hit and throws when the lists differ.
+  // MMT_LOCALMAP_CACHE_WAYS (1-8, default 4): that many lists of the current epoch are kept, the
+  // least recently used one replaced (the counted keyframe set flickers at its margin from frame
+  // to frame and comes back: §5h of DESIGN.md).
+  int lpc_mode_ = 1, lpc_ways_ = 4;
+  struct LpcEntry {
+    std::vector<int> kfs, pts;
+    long gen = 0, used = 0;
+    bool valid = false;
+  };
+  static constexpr int kLpcMaxWays = 8;
+  LpcEntry lpc_[kLpcMaxWays];
+  std::vector<int> lpc_check_;
+  long lpc_epoch_ = -1, lpc_tick_ = 0, lpc_hits_ = 0, lpc_rebuilds_ = 0, lpc_new_epoch_ = 0;
+  long ids_uploads_ = 0;
+  long list_gen_ = 0;                  // the last generation handed out
+  long local_gen_ = 0, spec_gen_ = 0;  // the generations of localPts_ and spec_pts_
   // compute_distinctive's pairwise descriptor distances of points with more than 32 good
   // observations, by observation ((keyframe << 32) | key, keyframe order)
   struct DistCache {
@@ -453,14 +494,19 @@ class MapEngine {
   PoolUpdate* d_up_ = nullptr;
   PoolUpdate* h_up_ = nullptr;
   int up_cap_ = 0;
-  // C3's one upload: [D1 descriptor][ids m][skip m][taken n] and, for D1's edge list, the keys
-  // bound before the search: [positions 3n floats][flags n] (sel_layout)
+  // C3's per-frame upload: [D1 descriptor][skip m][taken n] and, for D1's edge list, the keys
+  // bound before the search: [positions 3n floats][flags n] (SelLayout; the ids: d_ids_ below)
   uint8_t* d_sel_ = nullptr;
   uint8_t* h_sel_ = nullptr;
   uint8_t* d_inview_ = nullptr;
   uint8_t* h_inview_ = nullptr;
   CandSet c3_{};
   int local_cap_ = 0;
+  // the local points' handles (C3's ids), resident: uploaded on s_ when the list's generation
+  // differs from the one on the device (MMT_LOCALMAP_CACHE=0: in the upload block every frame)
+  int* d_ids_ = nullptr;
+  int* h_ids_ = nullptr;
+  long ids_gen_ = -1;
   // ---- LocalMapping
   GridFrame G_{};
   MappingStats mstats_;

@@ -58,9 +58,11 @@ MapEngine::~MapEngine() {
     }
     fprintf(stderr, "[mmt map profile] per frame: %.1f local keyframes, %.1f local points, "
             "%.1f C3 edges; %zu map points allocated, %d keyframes at the end; local map "
-            "speculated %ld times, taken %ld\n",
+            "speculated %ld times, taken %ld; local point list cache (MMT_LOCALMAP_CACHE=%d) "
+            "hits %ld, rebuilds %ld (%ld of them after a structure edit, %ld ids uploads)\n",
             prof_cnt_[0] / prof_n_, prof_cnt_[1] / prof_n_, prof_cnt_[2] / prof_n_, pts_.size(),
-            n_keyframes(), spec_tries_, spec_hits_);
+            n_keyframes(), spec_tries_, spec_hits_, lpc_mode_, lpc_hits_, lpc_rebuilds_,
+            lpc_new_epoch_, ids_uploads_);
   }
   if (s_) (void)hipStreamSynchronize(s_);
   if (lm_s_) {
@@ -80,11 +82,12 @@ static size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // C3's upload block for m local points and n keys: offsets of taken (after ids, skip), the base
 // positions and their flags, and the total size
+// (ids_inline false: the ids have a buffer of their own and no room here)
 struct SelLayout {
   size_t ids, skip, taken, bX, bHas, total;
-  SelLayout(int m, int n) {
+  SelLayout(int m, int n, bool ids_inline = true) {
     ids = kDescBytes;
-    skip = ids + 4 * (size_t)m;
+    skip = ids + (ids_inline ? 4 * (size_t)m : 0);
     taken = skip + m;
     bX = align16(taken + n);
     bHas = bX + 12 * (size_t)n;
@@ -120,6 +123,9 @@ void MapEngine::setup(const MapCamH& cam, int kcap) {
   prof_on_ = getenv("MMT_MAP_PROFILE") != nullptr;
   if (const char* e = getenv("MMT_LOCALMAP_SPEC")) spec_on_ = atoi(e) != 0;
   if (const char* e = getenv("MMT_OVERLAP_C3")) overlap_c3_ = atoi(e) != 0;
+  if (const char* e = getenv("MMT_LOCALMAP_CACHE")) lpc_mode_ = std::min(2, std::max(0, atoi(e)));
+  if (const char* e = getenv("MMT_LOCALMAP_CACHE_WAYS"))
+    lpc_ways_ = std::min(kLpcMaxWays, std::max(1, atoi(e)));
   h_early_ = pinned<uint8_t>(kOutHdr + 4 * (size_t)kcap);
   MMT_HIP(hipEventCreateWithFlags(&ev_early_, hipEventDisableTiming));
   // LocalMapping's stream, normal priority (high / low measured within noise / slower in round 5,
@@ -147,13 +153,14 @@ void MapEngine::grow_local(int m) {
   if (m <= local_cap_ && d_sel_) return;
   const int cap = std::max(m + 4096, 2 * local_cap_);
   void* old[] = {d_sel_, h_sel_, d_inview_, h_inview_, c3_.key, c3_.idx, c3_.n, c3_.win,
-                 c3_.choice};
+                 c3_.choice, d_ids_, h_ids_};
   if (s_) MMT_HIP(hipStreamSynchronize(s_));
-  for (int i = 0; i < 9; i++) {
+  for (int i = 0; i < 11; i++) {
     if (!old[i]) continue;
-    auto it = std::find(i == 1 || i == 3 ? hallocs_.begin() : dallocs_.begin(),
-                        i == 1 || i == 3 ? hallocs_.end() : dallocs_.end(), old[i]);
-    if (i == 1 || i == 3) {
+    const bool host = i == 1 || i == 3 || i == 10;
+    auto it = std::find(host ? hallocs_.begin() : dallocs_.begin(),
+                        host ? hallocs_.end() : dallocs_.end(), old[i]);
+    if (host) {
       (void)hipHostFree(old[i]);
       hallocs_.erase(it);
     } else {
@@ -168,6 +175,9 @@ void MapEngine::grow_local(int m) {
   h_inview_ = pinned<uint8_t>(cap);
   c3_ = CandSet{dev<uint32_t>((size_t)cap * kCandK), dev<int>((size_t)cap * kCandK), dev<int>(cap),
                 dev<PointWin>(cap), dev<int>(cap)};
+  d_ids_ = dev<int>(cap);
+  h_ids_ = pinned<int>(cap);
+  ids_gen_ = -1;  // the new buffer holds no list
   local_cap_ = cap;
 }
 
@@ -185,6 +195,8 @@ void MapEngine::reset() {
   refKF_ = -1;
   localKFs_.clear();
   localPts_.clear();
+  local_gen_ = ++list_gen_;
+  struct_epoch_++;
   recent_.clear();
   dirty_.clear();
   hasTlr_ = false;
@@ -247,7 +259,10 @@ void MapEngine::mark_bad(int h) {
   MPoint& p = mp(h);
   if (!p.bad && h < kTemp) n_good_--;
   p.bad = true;
-  if (h < kTemp) hot_[h].bad = 1;
+  if (h < kTemp) {
+    hot_[h].bad = 1;
+    struct_epoch_++;
+  }
   if (!dcache_.empty()) dcache_.erase(h);  // a bad point's descriptor is never recomputed
 }
 
@@ -256,7 +271,7 @@ void MapEngine::set_bad(int h) {  // MapPoint::SetBadFlag
   mark_bad(h);
   const std::vector<std::pair<int, int>> o = p.obs;
   p.obs.clear();
-  for (const auto& kv : o) kfs_[kv.first].mps[kv.second] = -1;
+  for (const auto& kv : o) kf_set_mp(kv.first, kv.second, -1);
   mark_dirty(h);
 }
 
@@ -389,6 +404,7 @@ int MapEngine::new_keyframe(const MapFrameH& C, const float* Tcw) {  // KeyFrame
   k.depth.assign(C.depth, C.depth + C.n);
   k.desc.assign(C.desc, C.desc + 32 * (size_t)C.n);
   k.mps = C.mps;
+  struct_epoch_++;
   return (int)kfs_.size() - 1;
 }
 
@@ -399,6 +415,7 @@ void MapEngine::update_best_covisibles(int kf) {  // KeyFrame::UpdateBestCovisib
   std::sort(v.begin(), v.end());
   K.ordered.clear();
   for (auto it = v.rbegin(); it != v.rend(); ++it) K.ordered.push_back(it->second);
+  struct_epoch_++;
 }
 
 void MapEngine::add_connection(int kf, int other, int w) {  // KeyFrame::AddConnection
@@ -442,6 +459,7 @@ void MapEngine::update_connections(int kf) {  // KeyFrame::UpdateConnections
   std::sort(v.begin(), v.end());
   KFrame& K = kfs_[kf];
   K.conn = counter;
+  struct_epoch_++;  // ordered, and the first connection's parent and children
   K.ordered.clear();
   for (auto it = v.rbegin(); it != v.rend(); ++it) K.ordered.push_back(it->second);
   if (K.firstConnection && K.id != 0) {
@@ -762,7 +780,7 @@ void MapEngine::initialize(MapFrameH& C, const float* Tcw) {
       unproject(cam_, Tcw, C.kps[i].x, C.kps[i].y, z, x3D);
       const int h = new_point_kf(x3D, kf);
       add_observation(h, kf, i);
-      kfs_[kf].mps[i] = h;
+      kf_set_mp(kf, i, h);
       compute_distinctive(h);
       update_normal_depth(h);
       C.mps[i] = h;
@@ -772,10 +790,12 @@ void MapEngine::initialize(MapFrameH& C, const float* Tcw) {
   map_point_culling(kf);
   local_mapping(kf);  // keyframe 0 never enters the database (LoopClosing.cc:95)
   lastKFFrameId_ = C.id;
+  struct_epoch_++;
   localKFs_.assign(1, kf);
   localPts_.clear();
   for (size_t h = 0; h < pts_.size(); h++)
     if (!pts_[h].bad) localPts_.push_back((int)h);  // mpMap->GetAllMapPoints()
+  local_gen_ = ++list_gen_;
   refKF_ = kf;
   C.refKF = kf;
   state_ = 1;
@@ -1001,10 +1021,57 @@ void MapEngine::update_local_keyframes(MapFrameH& C) {  // Tracking::UpdateLocal
   }
 }
 
-void MapEngine::update_local_points() { collect_local_points(localKFs_, localPts_); }
+void MapEngine::update_local_points() {
+  collect_local_points(localKFs_, localPts_, local_gen_);
+}
 
-void MapEngine::collect_local_points(const std::vector<int>& kfl, std::vector<int>& out) {
-  // Tracking::UpdateLocalPoints over the keyframes kfl
+// Tracking::UpdateLocalPoints over the keyframes kfl.  Between two keyframes nothing the walk
+// reads changes, and with the dense covisibility of the vocabulary path the keyframe list is the
+// frame before's too: the walk's result is kept and handed out again while the keyframe list and
+// the structure epoch (mmt_map.h) stay as they were when it was built.
+void MapEngine::collect_local_points(const std::vector<int>& kfl, std::vector<int>& out,
+                                     long& gen) {
+  LpcEntry* hit = nullptr;
+  if (lpc_mode_ != 0 && lpc_epoch_ == struct_epoch_)
+    for (int w = 0; w < lpc_ways_ && !hit; w++)
+      if (lpc_[w].valid && lpc_[w].kfs == kfl) hit = &lpc_[w];
+  if (hit) {
+    if (gen != hit->gen) {  // (a vector that holds this generation already stays as it is)
+      out = hit->pts;
+      gen = hit->gen;
+    }
+    hit->used = ++lpc_tick_;
+    lpc_hits_++;
+    if (lpc_mode_ == 2) {
+      walk_local_points(kfl, lpc_check_);
+      if (lpc_check_ != out)
+        throw DeviceError("local point list cache: the cached list differs from the walk's (" +
+                          std::to_string(out.size()) + " / " + std::to_string(lpc_check_.size()) +
+                          " points, frame " + std::to_string(curId_) + ")");
+    }
+    return;
+  }
+  walk_local_points(kfl, out);
+  gen = ++list_gen_;
+  lpc_rebuilds_++;
+  if (lpc_mode_ != 0) {
+    if (lpc_epoch_ != struct_epoch_) {  // (the other rebuilds: another keyframe list)
+      lpc_new_epoch_++;
+      for (LpcEntry& e : lpc_) e.valid = false;
+      lpc_epoch_ = struct_epoch_;
+    }
+    LpcEntry* v = &lpc_[0];  // the first free entry, or the least recently used one
+    for (int w = 0; w < lpc_ways_ && v->valid; w++)
+      if (!lpc_[w].valid || lpc_[w].used < v->used) v = &lpc_[w];
+    v->kfs = kfl;
+    v->pts = out;
+    v->gen = gen;
+    v->used = ++lpc_tick_;
+    v->valid = true;
+  }
+}
+
+void MapEngine::walk_local_points(const std::vector<int>& kfl, std::vector<int>& out) {
   out.clear();
   // a keyframe's slots are about half empty (-1) in no predictable pattern: its handles are first
   // compacted without a branch, then visited in slot order (the same points in the same order).
@@ -1073,7 +1140,7 @@ void MapEngine::speculate_local_map(const MapFrameH& L, int n) {
   expand_local_kfs(
       spec_kfs_, [&](int id) { return spec_mark_[id] == stamp; },
       [&](int id) { spec_mark_[id] = stamp; });
-  collect_local_points(spec_kfs_, spec_pts_);
+  collect_local_points(spec_kfs_, spec_pts_, spec_gen_);
   spec_valid_ = true;
   spec_tries_++;
 }
@@ -1126,6 +1193,7 @@ bool MapEngine::commit_local_map(MapFrameH& C) {
   for (const int id : spec_kfs_) kfs_[id].trackRef = curId_;
   localKFs_.swap(spec_kfs_);
   localPts_.swap(spec_pts_);
+  std::swap(local_gen_, spec_gen_);
   if (kmax >= 0) {
     refKF_ = kmax;
     C.refKF = kmax;
@@ -1153,14 +1221,23 @@ void MapEngine::search_local_points(MapFrameH& C, const GridFrame& G, const floa
   const int m = (int)localPts_.size();
   grow_local(m);
   gpu_flush_pool();
-  const SelLayout sl(m, C.n);
-  int* ids = (int*)(h_sel_ + sl.ids);
+  // the handles stay on the device while the list is the one uploaded last (its generation); the
+  // upload is ordered on s_ behind the previous frame's chain, which has completed (this function
+  // ends with a synchronisation), so h_ids_ is free to refill.  MMT_LOCALMAP_CACHE=0: in the
+  // upload block, every frame
+  const bool ids_inline = lpc_mode_ == 0;
+  const SelLayout sl(m, C.n, ids_inline);
+  const bool ids_new = ids_inline || ids_gen_ != local_gen_;
+  int* ids = ids_inline ? (int*)(h_sel_ + sl.ids) : h_ids_;
+  const int* d_ids = ids_inline ? (const int*)(d_sel_ + sl.ids) : d_ids_;
   uint8_t* skip = h_sel_ + sl.skip;
   uint8_t* taken = h_sel_ + sl.taken;
+  if (ids_new) {
+    memcpy(ids, localPts_.data(), 4 * (size_t)m);
+    ids_uploads_++;
+  }
   for (int j = 0; j < m; j++) {
-    const int h = localPts_[j];
-    const PtHot& q = hot_[h];
-    ids[j] = h;
+    const PtHot& q = hot_[localPts_[j]];
     skip[j] = q.lastSeen == (int)curId_ || q.bad;
   }
   // the keys bound before the search: taken (Observations() > 0) and, for D1's edge list, their
@@ -1182,14 +1259,18 @@ void MapEngine::search_local_points(MapFrameH& C, const GridFrame& G, const floa
   if (prof_on_) prof_[10] += now_us() - t_pack;
   pose_desc_fill(h_sel_, d_sel_, Tcw);
   MMT_HIP(hipMemcpyAsync(d_sel_, h_sel_, sl.total, hipMemcpyHostToDevice, s_));
+  if (!ids_inline && ids_new) {
+    if (m > 0) MMT_HIP(hipMemcpyAsync(d_ids_, h_ids_, 4 * (size_t)m, hipMemcpyHostToDevice, s_));
+    ids_gen_ = local_gen_;
+  }
   // ORBmatcher(0.8)::SearchByProjection's th: 3 for RGB-D, 5 right after a relocalisation
   const float th = curId_ < lastRelocFrameId_ + 2 ? 5.f : 3.f;
-  LocalSel sel{(const int*)(d_sel_ + sl.ids), d_sel_ + sl.skip, d_inview_};
+  LocalSel sel{d_ids, d_sel_ + sl.skip, d_inview_};
   // D1 over every key bound after the search (Tracking.cc:3189-3200), chained on the device: the
   // matcher kernel builds its edge list from the final bindings
   MapEdgeArgs e = edge_args(G);
   e.pool = d_pool_;
-  e.ids = (const int*)(d_sel_ + sl.ids);
+  e.ids = d_ids;
   e.has_base = d_sel_ + sl.bHas;
   e.base_X = (const float*)(d_sel_ + sl.bX);
   launch_search_local(G, Tcw, d_pool_, d_pool_desc_, m, th, d_sel_ + sl.taken, nullptr, c3_,
@@ -1304,7 +1385,7 @@ void MapEngine::create_new_keyframe(MapFrameH& C, const float* Tcw) {  // Tracki
         unproject(cam_, Tcw, C.kps[i].x, C.kps[i].y, C.depth[i], x3D);
         const int h = new_point_kf(x3D, kf);
         add_observation(h, kf, i);
-        kfs_[kf].mps[i] = h;
+        kf_set_mp(kf, i, h);
         compute_distinctive(h);
         update_normal_depth(h);
         C.mps[i] = h;
