@@ -14,21 +14,10 @@
 #include <vector>
 
 #include "../../include/mmt.h"
+#include "mmt_bowvec.h"  // BowVecH, FeatVecH
 #include "mmt_match.h"
 
 namespace mmt {
-
-// DBoW2::BowVector (std::map<WordId, WordValue>) and FeatureVector (std::map<NodeId,
-// std::vector<unsigned int>>) as flat arrays (words / nodes ascending)
-struct BowVecH {
-  std::vector<uint32_t> word;
-  std::vector<double> value;
-};
-struct FeatVecH {
-  std::vector<uint32_t> node;
-  std::vector<int> start{0};
-  std::vector<int> feat;
-};
 
 // The vocabulary tree on the device: node descriptors and the children in CSR (file order)
 struct VocDev {

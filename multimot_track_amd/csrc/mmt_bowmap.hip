@@ -211,25 +211,25 @@ void MapEngine::frame_bow(MapFrameH& C, const GridFrame& G) {  // Frame::Compute
 // KeyFrame::ComputeBoW on the keyframe-store copy (lm_s_), in two halves: ProcessNewKeyFrame's
 // host work runs between them (it does not read the vectors)
 void MapEngine::kf_bow_launch(int kf) {
-  const KFrame& K = kfs_[kf];
-  if (!K.hasBow) bow_launch(K.dev.g.desc, (int)K.keys.size(), lm_s_);
+  const KFrame& K = graph_.kf(kf);
+  if (!K.hasBow) bow_launch(kf_dev_[kf].g.desc, (int)K.keys.size(), lm_s_);
 }
 
 void MapEngine::kf_bow_finish(int kf) {
-  KFrame& K = kfs_[kf];
+  KFrame& K = graph_.kf(kf);
   if (K.hasBow) return;
   bow_finish((int)K.keys.size(), lm_s_, K.bow, K.fv);
   K.hasBow = true;
 }
 
 void MapEngine::kfdb_add(int kf) {  // KeyFrameDatabase::add
-  for (uint32_t w : kfs_[kf].bow.word) invfile_[w].push_back(kf);
+  for (uint32_t w : graph_.kf(kf).bow.word) invfile_[w].push_back(kf);
   bstats_.n_kfdb++;
 }
 
 void MapEngine::kfdb_erase(int kf) {  // KeyFrameDatabase::erase
   if (!voc_) return;
-  for (uint32_t w : kfs_[kf].bow.word) {
+  for (uint32_t w : graph_.kf(kf).bow.word) {
     std::vector<int>& l = invfile_[w];
     auto it = std::find(l.begin(), l.end(), kf);
     if (it != l.end()) l.erase(it);
@@ -241,7 +241,7 @@ std::vector<int> MapEngine::detect_relocalization_candidates(const MapFrameH& C)
   std::vector<int> shared;
   for (uint32_t w : C.bow.word)
     for (int k : invfile_[w]) {
-      KFrame& K = kfs_[k];
+      KFrame& K = graph_.kf(k);
       if (K.relocQuery != C.id) {
         K.relocWords = 0;
         K.relocQuery = C.id;
@@ -251,11 +251,11 @@ std::vector<int> MapEngine::detect_relocalization_candidates(const MapFrameH& C)
     }
   if (shared.empty()) return {};
   int maxCommonWords = 0;
-  for (int k : shared) maxCommonWords = std::max(maxCommonWords, kfs_[k].relocWords);
+  for (int k : shared) maxCommonWords = std::max(maxCommonWords, graph_.kf(k).relocWords);
   const int minCommonWords = (int)(maxCommonWords * 0.8f);
   std::vector<std::pair<float, int>> scored;
   for (int k : shared) {
-    KFrame& K = kfs_[k];
+    KFrame& K = graph_.kf(k);
     if (K.relocWords > minCommonWords) {
       const float si = (float)voc_->score(C.bow, K.bow);
       K.relocScore = si;
@@ -268,9 +268,9 @@ std::vector<int> MapEngine::detect_relocalization_candidates(const MapFrameH& C)
   for (const auto& sk : scored) {
     float bestScore = sk.first, accScore = bestScore;
     int bestKF = sk.second;
-    const std::vector<int>& o = kfs_[sk.second].ordered;  // GetBestCovisibilityKeyFrames(10)
+    const std::vector<int>& o = graph_.kf(sk.second).ordered();  // GetBestCovisibilityKeyFrames(10)
     for (size_t q = 0; q < o.size() && q < 10; q++) {
-      const KFrame& K2 = kfs_[o[q]];
+      const KFrame& K2 = graph_.kf(o[q]);
       if (K2.relocQuery != C.id) continue;
       accScore += K2.relocScore;
       if (K2.relocScore > bestScore) {
@@ -296,7 +296,7 @@ std::vector<int> MapEngine::detect_relocalization_candidates(const MapFrameH& C)
 // the keyframe key whose MapPoint now matches frame key i (-1); returns nmatches
 int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, float nnratio,
                                 std::vector<int>& match) {
-  const KFrame& K = kfs_[kf];
+  const KFrame& K = graph_.kf(kf);
   const int nk = (int)K.keys.size(), nF = C.n;
   const int nn1 = (int)K.fv.node.size(), nf1 = (int)K.fv.feat.size();
   const int nn2 = (int)C.fv.node.size(), nf2 = (int)C.fv.feat.size();
@@ -314,7 +314,7 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
                tot = o_c + 16;
   bw_grow(tot);
   uint8_t* h = h_bw_;
-  for (int i = 0; i < nk; i++) h[o_ok + i] = K.mps[i] >= 0 && !pts_[K.mps[i]].bad;
+  for (int i = 0; i < nk; i++) h[o_ok + i] = K.mps()[i] >= 0 && !graph_.mp(K.mps()[i]).bad();
   memcpy(h + o_n1, K.fv.node.data(), 4 * (size_t)nn1);
   memcpy(h + o_s1, K.fv.start.data(), 4 * (size_t)(nn1 + 1));
   memcpy(h + o_f1, K.fv.feat.data(), 4 * (size_t)nf1);
@@ -328,7 +328,8 @@ int MapEngine::search_by_bow_kf(int kf, const MapFrameH& C, const GridFrame& G, 
                      (const int*)(d + o_f1)};
   const BowFeatVec b{nn2, (const uint32_t*)(d + o_n2), (const int*)(d + o_s2),
                      (const int*)(d + o_f2)};
-  launch_search_by_bow(a, K.dev.g.keys, K.dev.g.desc, d + o_ok, b, G.keys, G.desc, nF, nnratio, 1,
+  const FuseKF& D = kf_dev_[kf];
+  launch_search_by_bow(a, D.g.keys, D.g.desc, d + o_ok, b, G.keys, G.desc, nF, nnratio, 1,
                        (int*)(d + o_m), (int*)(d + o_h), (int*)(d + o_c), (const int2*)(d + o_w),
                        nw, s_);
   MMT_HIP(hipMemcpyAsync(h + o_m, d + o_m, tot - o_m, hipMemcpyDeviceToHost, s_));
@@ -346,7 +347,7 @@ int MapEngine::gpu_pose_optimization(MapFrameH& C, float* Tcw) {
   int n = 0;
   for (int i = 0; i < C.n; i++) {
     if (C.mps[i] < 0) continue;
-    const MPoint& p = mp(C.mps[i]);
+    const MPoint& p = graph_.mp(C.mps[i]);
     memcpy(X + 3 * (size_t)n, p.pos, 12);
     ob[3 * (size_t)n] = C.kps[i].x;
     ob[3 * (size_t)n + 1] = C.kps[i].y;
@@ -379,8 +380,8 @@ bool MapEngine::track_reference_kf(MapFrameH& C, const GridFrame& G, float* Tcw,
   std::vector<int> match;
   int nmatches = search_by_bow_kf(refKF_, C, G, 0.7f, match);
   if (nmatches < 15) return false;
-  const KFrame& K = kfs_[refKF_];
-  for (int i = 0; i < C.n; i++) C.mps[i] = match[i] >= 0 ? K.mps[match[i]] : -1;
+  const KFrame& K = graph_.kf(refKF_);
+  for (int i = 0; i < C.n; i++) C.mps[i] = match[i] >= 0 ? K.mps()[match[i]] : -1;
   memcpy(Tcw, Tlast, 64);
   gpu_pose_optimization(C, Tcw);
   int nmatchesMap = 0;
@@ -504,14 +505,14 @@ struct EngineStage : Stage {  // MapEngine's d_bw_ / h_bw_
 // the keyframe's map points that are neither bad nor found, gathered for sbp_kf_flat
 int MapEngine::search_by_projection_kf(MapFrameH& C, const GridFrame& G, const float* Tcw, int kf,
                                        const std::set<int>& found, float th, int orbDist) {
-  const KFrame& K = kfs_[kf];
+  const KFrame& K = graph_.kf(kf);
   std::vector<int> hnd;
   std::vector<SbpKfPoint> P;
   std::vector<float> angle;
-  for (size_t i = 0; i < K.mps.size(); i++) {
-    const int h = K.mps[i];
-    if (h < 0 || pts_[h].bad || found.count(h)) continue;
-    const MPoint& p = pts_[h];
+  for (size_t i = 0; i < K.mps().size(); i++) {
+    const int h = K.mps()[i];
+    if (h < 0 || graph_.mp(h).bad() || found.count(h)) continue;
+    const MPoint& p = graph_.mp(h);
     SbpKfPoint q;
     memcpy(q.Xw, p.pos, 12);
     q.min_dist = p.minDist;
@@ -556,8 +557,8 @@ bool MapEngine::relocalization(MapFrameH& C, const GridFrame& G, float* Tcw) {
   std::vector<uint8_t> discarded(nKFs, 0);
   int nCandidates = 0;
   for (int i = 0; i < nKFs; i++) {
-    const KFrame& K = kfs_[cands[i]];
-    if (K.bad) {
+    const KFrame& K = graph_.kf(cands[i]);
+    if (K.bad()) {
       discarded[i] = 1;
       continue;
     }
@@ -565,7 +566,7 @@ bool MapEngine::relocalization(MapFrameH& C, const GridFrame& G, float* Tcw) {
     const int nm = search_by_bow_kf(cands[i], C, G, 0.75f, match);
     matches[i].assign(N, -1);
     for (int j = 0; j < N; j++)
-      if (match[j] >= 0) matches[i][j] = K.mps[match[j]];
+      if (match[j] >= 0) matches[i][j] = K.mps()[match[j]];
     if (nm < 15) {
       discarded[i] = 1;
       continue;
@@ -573,12 +574,12 @@ bool MapEngine::relocalization(MapFrameH& C, const GridFrame& G, float* Tcw) {
     Solver& S = solvers[i];
     for (int j = 0; j < N; j++) {
       const int h = matches[i][j];
-      if (h < 0 || pts_[h].bad) continue;
+      if (h < 0 || graph_.mp(h).bad()) continue;
       S.p2.push_back(C.kps[j].x);
       S.p2.push_back(C.kps[j].y);
       const float sc = cam_.scale[C.kps[j].octave];
       S.s2.push_back(sc * sc);
-      S.p3.insert(S.p3.end(), pts_[h].pos, pts_[h].pos + 3);
+      S.p3.insert(S.p3.end(), graph_.mp(h).pos, graph_.mp(h).pos + 3);
       S.kpIdx.push_back(j);
     }
     S.best_mask.assign(std::max<size_t>(S.kpIdx.size(), 1), 0);
@@ -766,31 +767,31 @@ int sft_flat(const MapCamH& cam, const SftKeyFrame& K1, int np, const SftKeyFram
 void MapEngine::create_new_map_points(int kf) {
   std::vector<int> neigh;
   {
-    const std::vector<int>& o = kfs_[kf].ordered;
+    const std::vector<int>& o = graph_.kf(kf).ordered();
     for (size_t q = 0; q < o.size() && q < 10; q++) neigh.push_back(o[q]);
   }
   const float ratioFactor = 1.5f * cam_.scale[1];
   const float mb = cam_.bf / cam_.fx;
   std::vector<int> pairs;
   for (int k2 : neigh) {
-    const KFrame& K1 = kfs_[kf];
-    const KFrame& K2 = kfs_[k2];
+    const KFrame& K1 = graph_.kf(kf);
+    const KFrame& K2 = graph_.kf(k2);
     const float vB[3] = {K2.Ow[0] - K1.Ow[0], K2.Ow[1] - K1.Ow[1], K2.Ow[2] - K1.Ow[2]};
     if (norm3(vB) < mb) continue;
     pairs.push_back(k2);
   }
   if (pairs.empty()) return;
-  const int np = (int)pairs.size(), n1 = (int)kfs_[kf].keys.size();
+  const int np = (int)pairs.size(), n1 = (int)graph_.kf(kf).keys.size();
   std::vector<std::vector<uint8_t>> has(np + 1);
   auto view = [&](int k, std::vector<uint8_t>& flags) {
-    const KFrame& K = kfs_[k];
+    const KFrame& K = graph_.kf(k);
     flags.resize(K.keys.size() + 1);
-    for (size_t i = 0; i < K.keys.size(); i++) flags[i] = K.mps[i] >= 0;
+    for (size_t i = 0; i < K.keys.size(); i++) flags[i] = K.mps()[i] >= 0;
     SftKeyFrame v;
     v.n = (int)K.keys.size();
-    v.d_keys = K.dev.g.keys;
-    v.d_desc = K.dev.g.desc;
-    v.d_uR = K.dev.uR;
+    v.d_keys = kf_dev_[k].g.keys;
+    v.d_desc = kf_dev_[k].g.desc;
+    v.d_uR = kf_dev_[k].uR;
     v.fv = BowFeatVec{(int)K.fv.node.size(), K.fv.node.data(), K.fv.start.data(), K.fv.feat.data()};
     v.has_mp = flags.data();
     v.Tcw = K.Tcw;
@@ -814,18 +815,18 @@ void MapEngine::create_new_map_points(int kf) {
     std::vector<std::pair<int, int>> mp12;
     for (int i = 0; i < n1; i++) {
       const int idx2 = match12[(size_t)p * (size_t)n1 + i];
-      if (idx2 >= 0 && kfs_[kf].mps[i] < 0) mp12.push_back({i, idx2});
+      if (idx2 >= 0 && graph_.kf(kf).mps()[i] < 0) mp12.push_back({i, idx2});
     }
     bstats_.n_sft_matches += (long)mp12.size();
-    const float* T1 = kfs_[kf].Tcw;
-    const float* T2 = kfs_[k2].Tcw;
+    const float* T1 = graph_.kf(kf).Tcw;
+    const float* T2 = graph_.kf(k2).Tcw;
     for (const auto& pr : mp12) {
       const int idx1 = pr.first, idx2 = pr.second;
-      const mmt_kp& kp1 = kfs_[kf].keys[idx1];
-      const float kp1_ur = kfs_[kf].uR[idx1];
+      const mmt_kp& kp1 = graph_.kf(kf).keys[idx1];
+      const float kp1_ur = graph_.kf(kf).uR[idx1];
       const bool bStereo1 = kp1_ur >= 0;
-      const mmt_kp& kp2 = kfs_[k2].keys[idx2];
-      const float kp2_ur = kfs_[k2].uR[idx2];
+      const mmt_kp& kp2 = graph_.kf(k2).keys[idx2];
+      const float kp2_ur = graph_.kf(k2).uR[idx2];
       const bool bStereo2 = kp2_ur >= 0;
       const float xn1[3] = {(kp1.x - cam_.cx) * cam_.invfx, (kp1.y - cam_.cy) * cam_.invfy, 1.0f};
       const float xn2[3] = {(kp2.x - cam_.cx) * cam_.invfx, (kp2.y - cam_.cy) * cam_.invfy, 1.0f};
@@ -849,9 +850,9 @@ void MapEngine::create_new_map_points(int kf) {
       float cosParallaxStereo = cosParallaxRays + 1;
       float cosParallaxStereo1 = cosParallaxStereo, cosParallaxStereo2 = cosParallaxStereo;
       if (bStereo1)
-        cosParallaxStereo1 = std::cos(2 * std::atan2(mb / 2, kfs_[kf].depth[idx1]));
+        cosParallaxStereo1 = std::cos(2 * std::atan2(mb / 2, graph_.kf(kf).depth[idx1]));
       else if (bStereo2)
-        cosParallaxStereo2 = std::cos(2 * std::atan2(mb / 2, kfs_[k2].depth[idx2]));
+        cosParallaxStereo2 = std::cos(2 * std::atan2(mb / 2, graph_.kf(k2).depth[idx2]));
       cosParallaxStereo = std::min(cosParallaxStereo1, cosParallaxStereo2);
       float x3D[3];
       if (cosParallaxRays < cosParallaxStereo && cosParallaxRays > 0 &&
@@ -868,9 +869,9 @@ void MapEngine::create_new_map_points(int kf) {
         if (v4[3] == 0) continue;
         for (int r = 0; r < 3; r++) x3D[r] = (float)((double)v4[r] * (1.0 / (double)v4[3]));
       } else if (bStereo1 && cosParallaxStereo1 < cosParallaxStereo2) {
-        unproject(cam_, T1, kp1.x, kp1.y, kfs_[kf].depth[idx1], x3D);
+        unproject(cam_, T1, kp1.x, kp1.y, graph_.kf(kf).depth[idx1], x3D);
       } else if (bStereo2 && cosParallaxStereo2 < cosParallaxStereo1) {
-        unproject(cam_, T2, kp2.x, kp2.y, kfs_[k2].depth[idx2], x3D);
+        unproject(cam_, T2, kp2.x, kp2.y, graph_.kf(k2).depth[idx2], x3D);
       } else {
         continue;
       }
@@ -911,20 +912,22 @@ void MapEngine::create_new_map_points(int kf) {
         const float errX2 = u2 - kp2.x, errY2 = v2 - kp2.y, errX2_r = u2_r - kp2_ur;
         if ((errX2 * errX2 + errY2 * errY2 + errX2_r * errX2_r) > 7.8 * sigmaSquare2) continue;
       }
-      const float n1v[3] = {x3D[0] - kfs_[kf].Ow[0], x3D[1] - kfs_[kf].Ow[1], x3D[2] - kfs_[kf].Ow[2]};
-      const float n2v[3] = {x3D[0] - kfs_[k2].Ow[0], x3D[1] - kfs_[k2].Ow[1], x3D[2] - kfs_[k2].Ow[2]};
+      const float* O1 = graph_.kf(kf).Ow;
+      const float* O2 = graph_.kf(k2).Ow;
+      const float n1v[3] = {x3D[0] - O1[0], x3D[1] - O1[1], x3D[2] - O1[2]};
+      const float n2v[3] = {x3D[0] - O2[0], x3D[1] - O2[1], x3D[2] - O2[2]};
       const float dist1 = norm3(n1v), dist2 = norm3(n2v);
       if (dist1 == 0 || dist2 == 0) continue;
       const float ratioDist = dist2 / dist1;
       const float ratioOctave = cam_.scale[kp1.octave] / cam_.scale[kp2.octave];
       if (ratioDist * ratioFactor < ratioOctave || ratioDist > ratioOctave * ratioFactor) continue;
-      const int hnew = new_point_kf(x3D, kf);  // MapPoint(x3D, mpCurrentKeyFrame, mpMap)
-      add_observation(hnew, kf, idx1);
-      add_observation(hnew, k2, idx2);
-      kf_set_mp(kf, idx1, hnew);
-      kf_set_mp(k2, idx2, hnew);
-      compute_distinctive(hnew);
-      update_normal_depth(hnew);
+      const int hnew = graph_.new_point_kf(x3D, kf);  // MapPoint(x3D, mpCurrentKeyFrame, mpMap)
+      graph_.add_observation(hnew, kf, idx1);
+      graph_.add_observation(hnew, k2, idx2);
+      graph_.kf_set_mp(kf, idx1, hnew);
+      graph_.kf_set_mp(k2, idx2, hnew);
+      graph_.compute_distinctive(hnew);
+      graph_.update_normal_depth(hnew);
       recent_.push_back(hnew);
       bstats_.n_triangulated++;
     }

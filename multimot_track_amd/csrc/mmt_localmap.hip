@@ -59,7 +59,7 @@ void MapEngine::kf_store_add(int kf) {
   const size_t o_uR = o_desc + 32 * (size_t)kcap_;
   const size_t o_cs = o_uR + al16(4 * (size_t)kcap_);
   const size_t o_ci = o_cs + al16(4 * (size_t)(kGridCells + 1));
-  KFrame& K = kfs_[kf];
+  if (kf_dev_.size() <= (size_t)kf) kf_dev_.resize((size_t)kf + 1);
   const int n = G_.n;
   MMT_HIP(hipMemcpyAsync(base, G_.keys, sizeof(mmt_kp) * (size_t)n, hipMemcpyDeviceToDevice, lm_s_));
   MMT_HIP(hipMemcpyAsync(base + o_desc, G_.desc, 32 * (size_t)n, hipMemcpyDeviceToDevice, lm_s_));
@@ -67,7 +67,7 @@ void MapEngine::kf_store_add(int kf) {
   MMT_HIP(hipMemcpyAsync(base + o_cs, G_.cell_start, 4 * (size_t)(kGridCells + 1),
                          hipMemcpyDeviceToDevice, lm_s_));
   MMT_HIP(hipMemcpyAsync(base + o_ci, G_.cell_idx, 4 * (size_t)n, hipMemcpyDeviceToDevice, lm_s_));
-  FuseKF& f = K.dev;
+  FuseKF& f = kf_dev_[kf];
   f.g.keys = (const mmt_kp*)base;
   f.g.desc = base + o_desc;
   f.uR = (const float*)(base + o_uR);
@@ -76,106 +76,12 @@ void MapEngine::kf_store_add(int kf) {
   f.n = n;
 }
 
-// ------------------------------------------------------------------ KeyFrame / MapPoint edits
-void MapEngine::set_pose(int kf, const float* T) {  // KeyFrame::SetPose
-  KFrame& K = kfs_[kf];
-  memcpy(K.Tcw, T, 64);
-  cam_centre(T, K.Ow);
-  mat4_eye(K.Twc);
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) K.Twc[4 * r + c] = T[4 * c + r];
-    K.Twc[4 * r + 3] = K.Ow[r];
-  }
-}
-
-void MapEngine::erase_observation(int h, int kf) {  // MapPoint::EraseObservation
-  MPoint& p = mp(h);
-  auto it = std::lower_bound(p.obs.begin(), p.obs.end(), std::make_pair(kf, INT_MIN));
-  if (it == p.obs.end() || it->first != kf) return;
-  if (kfs_[kf].uR[it->second] >= 0)
-    p.nObs -= 2;
-  else
-    p.nObs--;
-  p.obs.erase(it);
-  // an emptied map's begin() is undefined in the reference; the point goes bad right below then
-  if (p.refKF == kf) p.refKF = p.obs.empty() ? -1 : p.obs.front().first;
-  if (p.nObs <= 2) set_bad(h);
-}
-
-void MapEngine::replace(int h, int by) {  // MapPoint::Replace (this = h, pMP = by)
-  if (h == by) return;
-  MPoint& p = mp(h);
-  const std::vector<std::pair<int, int>> obs = p.obs;
-  p.obs.clear();
-  mark_bad(h);
-  const int nvisible = p.visible, nfound = p.found;
-  p.replaced = by;
-  mark_dirty(h);
-  for (const auto& kv : obs) {
-    if (mp(by).obs_index(kv.first) < 0) {
-      kf_set_mp(kv.first, kv.second, by);  // ReplaceMapPointMatch
-      add_observation(by, kv.first, kv.second);
-    } else {
-      kf_set_mp(kv.first, kv.second, -1);  // EraseMapPointMatch(idx)
-    }
-  }
-  MPoint& q = mp(by);
-  q.found += nfound;
-  q.visible += nvisible;
-  compute_distinctive(by);
-}
-
-void MapEngine::erase_connection(int kf, int other) {  // KeyFrame::EraseConnection
-  if (kfs_[kf].conn.erase(other)) update_best_covisibles(kf);
-}
-
-void MapEngine::kf_set_bad(int kf) {  // KeyFrame::SetBadFlag (mbNotErase is never set here)
-  KFrame& K = kfs_[kf];
-  if (K.id == 0) return;
-  for (const auto& kv : std::map<int, int>(K.conn)) erase_connection(kv.first, kf);
-  for (size_t i = 0; i < K.mps.size(); i++)
-    if (K.mps[i] >= 0) erase_observation(K.mps[i], kf);
-  K.conn.clear();
-  K.ordered.clear();
-  // the spanning tree: each round re-parents the child with the strongest link to a candidate
-  std::set<int> cand;
-  cand.insert(K.parent);
-  while (!K.children.empty()) {
-    bool bContinue = false;
-    int mx = -1, pC = -1, pP = -1;
-    for (int ch : K.children) {
-      if (kfs_[ch].bad) continue;
-      for (int c : kfs_[ch].ordered)
-        for (int q : cand)
-          if (c == q) {
-            auto it = kfs_[ch].conn.find(c);  // GetWeight
-            const int wgt = it == kfs_[ch].conn.end() ? 0 : it->second;
-            if (wgt > mx) {
-              pC = ch;
-              pP = c;
-              mx = wgt;
-              bContinue = true;
-            }
-          }
-    }
-    if (!bContinue) break;
-    kfs_[pC].parent = pP;  // ChangeParent
-    kfs_[pP].children.insert(pC);
-    mstats_.n_reparent++;
-    cand.insert(pC);
-    K.children.erase(pC);
-  }
-  if (K.parent >= 0) {
-    for (int ch : K.children) {
-      kfs_[ch].parent = K.parent;
-      kfs_[K.parent].children.insert(ch);
-      mstats_.n_reparent++;
-    }
-    kfs_[K.parent].children.erase(kf);
-  }
-  K.bad = true;
-  struct_epoch_++;  // the bad flag, ordered, and the spanning tree's parents and children above
-  kfdb_erase(kf);  // mpKeyFrameDB->erase(this) (KeyFrame.cc:544)
+// KeyFrame::SetBadFlag: the graph's part, then mpKeyFrameDB->erase(this) (KeyFrame.cc:544)
+void MapEngine::kf_set_bad(int kf) {
+  if (graph_.kf(kf).id == 0) return;
+  graph_.kf_set_bad(kf);
+  mstats_.n_reparent = graph_.stats().n_reparent;
+  kfdb_erase(kf);
 }
 
 // ------------------------------------------------------------------ Fuse
@@ -200,8 +106,8 @@ void MapEngine::fuse_launch(const std::vector<int>& kft_kf, const std::vector<Fu
   }
   FuseKF* tab = (FuseKF*)h_fup_;
   for (size_t t = 0; t < kft_kf.size(); t++) {
-    const KFrame& K = kfs_[kft_kf[t]];
-    tab[t] = K.dev;
+    const KFrame& K = graph_.kf(kft_kf[t]);
+    tab[t] = kf_dev_[kft_kf[t]];
     memcpy(tab[t].Tcw, K.Tcw, 64);
     memcpy(tab[t].Ow, K.Ow, 12);
   }
@@ -238,18 +144,18 @@ void MapEngine::fuse_launch(const std::vector<int>& kft_kf, const std::vector<Fu
 // ORBmatcher::Fuse's decision for one point (ORBmatcher.cc:1326-1346)
 void MapEngine::fuse_apply(int kf, int h, int bestIdx, int bestDist) {
   if (bestDist > 50) return;  // TH_LOW
-  KFrame& K = kfs_[kf];
-  const int pin = K.mps[bestIdx];
+  KFrame& K = graph_.kf(kf);
+  const int pin = K.mps()[bestIdx];
   if (pin >= 0) {
-    if (!mp(pin).bad) {
-      if (mp(pin).nObs > mp(h).nObs)
-        replace(h, pin);
+    if (!graph_.mp(pin).bad()) {
+      if (graph_.mp(pin).nObs() > graph_.mp(h).nObs())
+        graph_.replace(h, pin);
       else
-        replace(pin, h);
+        graph_.replace(pin, h);
     }
   } else {
-    add_observation(h, kf, bestIdx);
-    kf_set_mp(kf, bestIdx, h);
+    graph_.add_observation(h, kf, bestIdx);
+    graph_.kf_set_mp(kf, bestIdx, h);
   }
   mstats_.n_fused++;
 }
@@ -267,12 +173,12 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
   std::vector<int> ver;
   for (int t = 0; t < nk; t++)
     for (int i = 0; i < np; i++) {
-      if (t == 0 && i + 8 < np) prefetch_point(pts[i + 8]);
+      if (t == 0 && i + 8 < np) graph_.prefetch_point(pts[i + 8]);
       const int h = pts[i];
-      if (h < 0 || mp(h).bad || mp(h).obs_index(kfl[t]) >= 0) continue;
+      if (h < 0 || graph_.mp(h).bad() || graph_.mp(h).obs_index(kfl[t]) >= 0) continue;
       qidx[(size_t)t * np + i] = (int)q.size();
       q.push_back(FuseQuery{t, h});
-      ver.push_back(mp(h).desc_ver);
+      ver.push_back(graph_.mp(h).desc_ver);
     }
   std::vector<int2> res(q.size());
   double tb = prof_on_ ? now_us() : 0;
@@ -283,8 +189,8 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
     for (int i = 0; i < np; i++) {
       const int h = pts[i];
       if (h < 0) continue;
-      const MPoint& p = mp(h);
-      if (p.bad || p.obs_index(kf) >= 0) continue;
+      const MPoint& p = graph_.mp(h);
+      if (p.bad() || p.obs_index(kf) >= 0) continue;
       const int qi = qidx[(size_t)t * np + i];
       if (qi < 0) continue;  // cannot happen (see above); defensive
       if (ver[qi] != p.desc_ver) {
@@ -296,7 +202,7 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
             const int q2 = qidx[(size_t)t2 * np + i2];
             if (q2 < 0) continue;
             const int h2 = pts[i2];
-            if (mp(h2).bad || ver[q2] == mp(h2).desc_ver) continue;
+            if (graph_.mp(h2).bad() || ver[q2] == graph_.mp(h2).desc_ver) continue;
             rq.push_back(FuseQuery{t2, h2});
             rpos.push_back(q2);
           }
@@ -304,7 +210,7 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
         fuse_launch(kfl, rq, rr.data());
         for (size_t k = 0; k < rq.size(); k++) {
           res[rpos[k]] = rr[k];
-          ver[rpos[k]] = mp(rq[k].h).desc_ver;
+          ver[rpos[k]] = graph_.mp(rq[k].h).desc_ver;
         }
         mstats_.fuse_relaunches++;
       }
@@ -317,34 +223,34 @@ void MapEngine::fuse_sequence(const std::vector<int>& kfl, const std::vector<int
 // ------------------------------------------------------------------ LocalMapping steps
 void MapEngine::search_in_neighbors(int kf) {  // LocalMapping::SearchInNeighbors (RGB-D: nn 10)
   double tb = prof_on_ ? now_us() : 0;
-  const long cur = kfs_[kf].id;
+  const long cur = graph_.kf(kf).id;
   auto best = [&](int k, size_t n) {
-    const std::vector<int>& o = kfs_[k].ordered;
+    const std::vector<int>& o = graph_.kf(k).ordered();
     return std::vector<int>(o.begin(), o.begin() + std::min(o.size(), n));
   };
   std::vector<int> targets;
   for (int k : best(kf, 10)) {
-    KFrame& Ki = kfs_[k];
-    if (Ki.bad || Ki.fuseTarget == cur) continue;
+    KFrame& Ki = graph_.kf(k);
+    if (Ki.bad() || Ki.fuseTarget == cur) continue;
     targets.push_back(k);
     Ki.fuseTarget = cur;
     for (int k2 : best(k, 5)) {
-      const KFrame& K2 = kfs_[k2];
-      if (K2.bad || K2.fuseTarget == cur || K2.id == cur) continue;
+      const KFrame& K2 = graph_.kf(k2);
+      if (K2.bad() || K2.fuseTarget == cur || K2.id == cur) continue;
       targets.push_back(k2);
     }
   }
-  const std::vector<int> matches = kfs_[kf].mps;
+  const std::vector<int> matches = graph_.kf(kf).mps();
   blk_time(2, tb);
   fuse_sequence(targets, matches);
   blk_time(3, tb);
   std::vector<int> cands;
   for (int t : targets) {
-    const std::vector<int> mps = kfs_[t].mps;
+    const std::vector<int> mps = graph_.kf(t).mps();
     for (int h : mps) {
       if (h < 0) continue;
-      MPoint& p = mp(h);
-      if (p.bad || p.fuseCand == cur) continue;
+      MPoint& p = graph_.mp(h);
+      if (p.bad() || p.fuseCand == cur) continue;
       p.fuseCand = cur;
       cands.push_back(h);
     }
@@ -352,69 +258,69 @@ void MapEngine::search_in_neighbors(int kf) {  // LocalMapping::SearchInNeighbor
   blk_time(4, tb);
   fuse_sequence(std::vector<int>{kf}, cands);
   blk_time(5, tb);
-  const std::vector<int> now = kfs_[kf].mps;
+  const std::vector<int> now = graph_.kf(kf).mps();
   for (size_t j = 0; j < now.size(); j++) {
-    if (j + 8 < now.size()) prefetch_point(now[j + 8]);
+    if (j + 8 < now.size()) graph_.prefetch_point(now[j + 8]);
     const int h = now[j];
-    if (h < 0 || mp(h).bad) continue;
-    compute_distinctive(h);
-    update_normal_depth(h);
+    if (h < 0 || graph_.mp(h).bad()) continue;
+    graph_.compute_distinctive(h);
+    graph_.update_normal_depth(h);
   }
   blk_time(6, tb);
-  update_connections(kf);
+  graph_.update_connections(kf);
   blk_time(7, tb);
 }
 
 void MapEngine::local_bundle_adjustment(int kf) {  // Optimizer::LocalBundleAdjustment
   const double t0 = prof_on_ ? now_us() : 0;
-  const long cur = kfs_[kf].id;
+  const long cur = graph_.kf(kf).id;
   std::vector<int> local{kf};
-  kfs_[kf].baLocal = cur;
-  for (int k : kfs_[kf].ordered) {  // GetVectorCovisibleKeyFrames
-    kfs_[k].baLocal = cur;
-    if (!kfs_[k].bad) local.push_back(k);
+  graph_.kf(kf).baLocal = cur;
+  for (int k : graph_.kf(kf).ordered()) {  // GetVectorCovisibleKeyFrames
+    graph_.kf(k).baLocal = cur;
+    if (!graph_.kf(k).bad()) local.push_back(k);
   }
   std::vector<int> lpts;
   for (int k : local)
-    for (int h : std::vector<int>(kfs_[k].mps)) {
+    for (int h : std::vector<int>(graph_.kf(k).mps())) {
       if (h < 0) continue;
-      MPoint& p = mp(h);
-      if (p.bad || p.baLocal == cur) continue;
+      MPoint& p = graph_.mp(h);
+      if (p.bad() || p.baLocal == cur) continue;
       lpts.push_back(h);
       p.baLocal = cur;
     }
   std::vector<int> fixedKFs;
   for (int h : lpts)
-    for (const auto& kv : mp(h).obs) {
-      KFrame& Ki = kfs_[kv.first];
+    for (const auto& kv : graph_.mp(h).obs()) {
+      KFrame& Ki = graph_.kf(kv.first);
       if (Ki.baLocal != cur && Ki.baFixed != cur) {
         Ki.baFixed = cur;
-        if (!Ki.bad) fixedKFs.push_back(kv.first);
+        if (!Ki.bad()) fixedKFs.push_back(kv.first);
       }
     }
   std::vector<int> verts = local;
   verts.insert(verts.end(), fixedKFs.begin(), fixedKFs.end());
   const int nK = (int)verts.size(), nP = (int)lpts.size();
   std::vector<int>& vIdx = ba_vidx_;  // keyframe -> vertex, -1 elsewhere (reset below)
-  if (vIdx.size() < kfs_.size()) vIdx.resize(kfs_.size(), -1);
+  if (vIdx.size() < graph_.n_kfs()) vIdx.resize(graph_.n_kfs(), -1);
   std::vector<float> Tv(16 * (size_t)nK), Xv(3 * (size_t)nP);
   std::vector<uint8_t> fixed(nK);
   int nO = 0;
   for (int v = 0; v < nK; v++) {
     vIdx[verts[v]] = v;
-    memcpy(&Tv[16 * (size_t)v], kfs_[verts[v]].Tcw, 64);
-    fixed[v] = v >= (int)local.size() || kfs_[verts[v]].id == 0;
+    memcpy(&Tv[16 * (size_t)v], graph_.kf(verts[v]).Tcw, 64);
+    fixed[v] = v >= (int)local.size() || graph_.kf(verts[v]).id == 0;
     nO += !fixed[v];
   }
   // edges point by point, each point's observations in keyframe order (Optimizer.cc:3460-3541)
   std::vector<int> e_pt, e_kf, e_kfid;
   std::vector<float> e_obs, e_s;
   for (int j = 0; j < nP; j++) {
-    const MPoint& p = mp(lpts[j]);
+    const MPoint& p = graph_.mp(lpts[j]);
     memcpy(&Xv[3 * (size_t)j], p.pos, 12);
-    for (const auto& kv : p.obs) {
-      const KFrame& Ki = kfs_[kv.first];
-      if (Ki.bad) continue;
+    for (const auto& kv : p.obs()) {
+      const KFrame& Ki = graph_.kf(kv.first);
+      if (Ki.bad()) continue;
       const mmt_kp& kp = Ki.keys[kv.second];
       e_pt.push_back(j);
       e_kf.push_back(vIdx[kv.first]);
@@ -459,42 +365,42 @@ void MapEngine::local_bundle_adjustment(int kf) {  // Optimizer::LocalBundleAdju
       const bool stereo = !(e_obs[3 * (size_t)i + 2] < 0);
       if (stereo != (pass == 1) || !er[i]) continue;
       const int h = lpts[e_pt[i]], k = e_kfid[i];
-      const int idx = mp(h).obs_index(k);  // KeyFrame::EraseMapPointMatch(pMP)
-      if (idx >= 0) kf_set_mp(k, idx, -1);
-      erase_observation(h, k);
+      const int idx = graph_.mp(h).obs_index(k);  // KeyFrame::EraseMapPointMatch(pMP)
+      if (idx >= 0) graph_.kf_set_mp(k, idx, -1);
+      graph_.erase_observation(h, k);
       mstats_.n_ba_erased++;
     }
-  for (size_t v = 0; v < local.size(); v++) set_pose(local[v], &Tout[16 * v]);
+  for (size_t v = 0; v < local.size(); v++) graph_.set_pose(local[v], &Tout[16 * v]);
   for (int j = 0; j < nP; j++) {
-    MPoint& p = mp(lpts[j]);
+    MPoint& p = graph_.mp(lpts[j]);
     memcpy(p.pos, &Xout[3 * (size_t)j], 12);  // SetWorldPos
-    mark_dirty(lpts[j]);
-    update_normal_depth(lpts[j]);
+    graph_.mark_dirty(lpts[j]);
+    graph_.update_normal_depth(lpts[j]);
   }
   blk_time(9, tb);
   if (prof_on_) mstats_.ba_us += now_us() - t0;
 }
 
 void MapEngine::keyframe_culling(int kf) {  // LocalMapping::KeyFrameCulling (RGB-D)
-  const std::vector<int> local = kfs_[kf].ordered;
+  const std::vector<int> local = graph_.kf(kf).ordered();
   for (int k : local) {
-    KFrame& K = kfs_[k];
+    KFrame& K = graph_.kf(k);
     if (K.id == 0) continue;
     const int thObs = 3;
     int nRedundant = 0, nMPs = 0;
-    for (size_t i = 0; i < K.mps.size(); i++) {
-      const int h = K.mps[i];
+    for (size_t i = 0; i < K.mps().size(); i++) {
+      const int h = K.mps()[i];
       if (h < 0) continue;
-      const MPoint& p = mp(h);
-      if (p.bad) continue;
+      const MPoint& p = graph_.mp(h);
+      if (p.bad()) continue;
       if (K.depth[i] > cam_.thDepth || K.depth[i] < 0) continue;
       nMPs++;
-      if (p.nObs > thObs) {
+      if (p.nObs() > thObs) {
         const int scaleLevel = K.keys[i].octave;
         int nObs = 0;
-        for (const auto& kv : p.obs) {
+        for (const auto& kv : p.obs()) {
           if (kv.first == k) continue;
-          if (kfs_[kv.first].keys[kv.second].octave <= scaleLevel + 1) {
+          if (graph_.kf(kv.first).keys[kv.second].octave <= scaleLevel + 1) {
             nObs++;
             if (nObs >= thObs) break;
           }

@@ -1,6 +1,7 @@
-// multimot_track_amd/csrc/mmt_map.h -- ORB-SLAM2 map tracking for RGB-D: the
-// MapPoint / KeyFrame state and Tracking's map branch that produce the ego pose the flow solve
-// (PoseOptimizationFlow2Cam, D2) starts from.
+// multimot_track_amd/csrc/mmt_map.h -- ORB-SLAM2 map tracking for RGB-D:
+// Tracking's map branch and LocalMapping over the map graph (MapPoint / KeyFrame state: class
+// MapGraph, mmt_mapgraph.h), which produce the ego pose the flow solve (PoseOptimizationFlow2Cam,
+// D2) starts from.
 //
 // Reference: MapPoint.cc, KeyFrame.cc, Map.cc; Tracking.cc:985-1176 (Track's map branch),
 // 2531-2575 (StereoInitialization), 2766-3612 (CheckReplacedInLastFrame, UpdateLastFrame,
@@ -30,16 +31,14 @@
 
 #include <cstdint>
 #include <functional>
-#include <map>
 #include <set>
-#include <unordered_map>
 #include <utility>
-#include <memory>
 #include <vector>
 
 #include "mmt_ba.h"
 #include "mmt_bow.h"
 #include "mmt_internal.h"
+#include "mmt_mapgraph.h"
 #include "mmt_match.h"
 #include "mmt_track.h"
 
@@ -53,80 +52,6 @@ struct MapCamH {
   int nlevels = 0;
   float logScale = 0;
   std::vector<float> scale, invSigma2;
-};
-
-// An array in chunks of 2^kShift elements: indexing as a vector's (one more load), push_back never
-// moves the elements already stored (references stay valid)
-template <class T, int kShift = 13>
-class ChunkArray {
- public:
-  T& operator[](size_t i) { return chunks_[i >> kShift][i & kMask]; }
-  const T& operator[](size_t i) const { return chunks_[i >> kShift][i & kMask]; }
-  size_t size() const { return n_; }
-  void push_back(const T& v) {
-    if ((n_ >> kShift) >= chunks_.size()) chunks_.emplace_back(new T[kChunk]);
-    (*this)[n_++] = v;
-  }
-  void clear() {
-    chunks_.clear();
-    n_ = 0;
-  }
-
- private:
-  static constexpr size_t kChunk = (size_t)1 << kShift, kMask = kChunk - 1;
-  std::vector<std::unique_ptr<T[]>> chunks_;
-  size_t n_ = 0;
-};
-
-struct MPoint {
-  float pos[3] = {0, 0, 0};
-  float normal[3] = {0, 0, 0};
-  float minDist = 0, maxDist = 0;
-  uint8_t desc[32] = {0};
-  std::vector<std::pair<int, int>> obs;  // mObservations (keyframe id, key index), id-ascending
-  int nObs = 0;
-  int refKF = -1;
-  int firstKFid = -1;
-  int visible = 1, found = 1;
-  bool bad = false;
-  bool trackInView = false;
-  bool dirty = false;  // pool record out of date
-  long lastSeen = 0;  // real points: mirrored in MapEngine::hot_ (the per-frame scans read that)
-  int replaced = -1;  // mpReplaced
-  long fuseCand = 0, baLocal = 0;  // mnFuseCandidateForKF, mnBALocalForKF
-  int desc_ver = 0;   // bumped by ComputeDistinctiveDescriptors (Fuse results read it)
-  int obs_index(int kf) const {
-    for (const auto& o : obs)
-      if (o.first == kf) return o.second;
-    return -1;
-  }
-};
-
-struct KFrame {
-  int id = 0;
-  long frameId = 0;
-  float Tcw[16], Twc[16], Ow[3];
-  std::vector<mmt_kp> keys;
-  std::vector<float> uR, depth;
-  std::vector<uint8_t> desc;
-  std::vector<int> mps;
-  std::map<int, int> conn;  // mConnectedKeyFrameWeights
-  std::vector<int> ordered;
-  bool firstConnection = true;
-  int parent = -1;
-  std::set<int> children;
-  long trackRef = 0;
-  bool bad = false;
-  long fuseTarget = 0, baLocal = 0, baFixed = 0;  // mnFuseTargetForKF, mnBALocalForKF, mnBAFixedForKF
-  FuseKF dev{};  // the keyframe's keys, descriptors, mvuRight and grid on the device (KF store)
-  // with a vocabulary: mBowVec, mFeatVec, and the KeyFrameDatabase query fields (KeyFrame.h:146-149;
-  // mRelocScore uninitialised in the reference: pinned 0)
-  BowVecH bow;
-  FeatVecH fv;
-  bool hasBow = false;
-  long relocQuery = 0;
-  int relocWords = 0;
-  float relocScore = 0;
 };
 
 // glibc's rand() (random_r TYPE_3, srand(1) for an unseeded process): the stream
@@ -150,26 +75,11 @@ struct MappingStats {
   // finer host wall times of the keyframe path (MMT_MAP_PROFILE; printed at destruction)
   double kfnew_us = 0, pnk_us = 0, sin_us = 0, basolve_us = 0, cull_us = 0, lmsync_us = 0;
   double cnmp_us = 0;  // CreateNewMapPoints (vocabulary path), inside sin_us
-  static constexpr int kBlk = 18;  // finer blocks of the keyframe path (names in ~MapEngine)
+  // finer blocks of the keyframe path (names in ~MapEngine; 14, ComputeDistinctiveDescriptors,
+  // and n_reparent are the graph's: MapGraph::Stats)
+  static constexpr int kBlk = 18;
   double blk_us[kBlk] = {};
   long n_lm = 0;
-};
-
-// The map-path view of one Frame: its ORB output and B3 arrays (host copies of the device ones)
-// and its map state.
-struct MapFrameH {
-  long id = 0;
-  int n = 0;
-  const mmt_kp* kps = nullptr;
-  const uint8_t* desc = nullptr;
-  const float* uR = nullptr;     // mvuRight
-  const float* depth = nullptr;  // mvDepth
-  std::vector<int> mps;          // mvpMapPoints (point handle or -1)
-  std::vector<uint8_t> outlier;  // mvbOutlier
-  int refKF = -1;                // mpReferenceKF
-  BowVecH bow;                   // mBowVec / mFeatVec (Frame::ComputeBoW, with a vocabulary)
-  FeatVecH fv;
-  bool hasBow = false;
 };
 
 // counters of the vocabulary path (tests, mmt_map_counters)
@@ -216,8 +126,8 @@ class MapEngine {
   // end of Track: mlRelativeFramePoses.push_back(Tcw * Tref^-1) (Tracking.cc:2481-2489)
   void frame_done(const MapFrameH& C, const float* Tcw);
   int state() const { return state_; }
-  int n_keyframes() const;
-  int n_mappoints() const { return n_good_; }
+  int n_keyframes() const { return graph_.n_keyframes(); }
+  int n_mappoints() const { return graph_.n_mappoints(); }
   // the current frame on the device (B3 grid, keys, descriptors): the keyframe made from it copies
   // them into the keyframe store, where Fuse reads them
   void set_frame_grid(const GridFrame& G) { G_ = G; }
@@ -229,19 +139,10 @@ class MapEngine {
     mstats_.blk_us[k] += n - t;
     t = n;
   }
-  // host prefetch of map point h's record (loops over point lists walk a 100k-point map in
-  // random order: one cache miss per record otherwise); MMT_NO_PREFETCH builds without it (A/B)
-  void prefetch_point(int h) const {
-#ifndef MMT_NO_PREFETCH
-    if (h >= 0 && h < kTemp && (size_t)h < pts_.size()) __builtin_prefetch(&pts_[h]);
-#else
-    (void)h;
-#endif
-  }
   // test knob: KeyFrameCulling's redundancy ratio (0.9 in the reference, LocalMapping.cc:697)
   void set_cull_ratio(double r) { cull_ratio_ = r; }
   // the map as flat arrays (mmt_map_dump, include/mmt.h): sizes[7]; arrays written when out != 0
-  void dump(int32_t* sizes, const mmt_map_dump_arrays* out) const;
+  void dump(int32_t* sizes, const mmt_map_dump_arrays* out) const { graph_.dump(sizes, out); }
   // System's vocabulary (System.cc:67): with one, TrackReferenceKeyFrame, Relocalization and
   // CreateNewMapPoints run as the reference's (mmt_bowmap.hip); without, the substitutes above
   void set_vocabulary(Vocabulary* v);
@@ -249,9 +150,14 @@ class MapEngine {
 
  private:
   std::function<void()> overlap_;
+  // The map graph (MapPoint / KeyFrame bookkeeping) and the local point list cache that reads it:
+  // the graph's guarded fields are written through its mutators only, each of which bumps the
+  // epoch the cache keys on (class MapGraph, mmt_mapgraph.h)
+  MapGraph graph_;
+  LocalPointCache lpc_;
+  std::vector<FuseKF> kf_dev_;  // per keyframe: its keys, descriptors, mvuRight and grid on the
+                                // device (the keyframe store, kf_store_add)
   std::vector<int> kf_count_, kf_touched_;  // update_local_keyframes' counter
-  std::vector<int> lp_buf_;                  // update_local_points' compacted slots
-  std::vector<uint64_t> lp_seen_;            // update_local_points' per-point marks (bits)
   // TrackLocalMap's local keyframes and points, computed from C2's matches while D1 runs on the
   // GPU (speculate_local_map) and taken by track_local_map when D1's outliers leave every counted
   // keyframe with a count (commit_local_map); MMT_LOCALMAP_SPEC=0 turns it off (A/B)
@@ -267,65 +173,17 @@ class MapEngine {
   void speculate_local_map(const MapFrameH& L, int n);
   bool commit_local_map(MapFrameH& C);
   void spec_discard();
-  template <class Marked, class Mark>
-  void expand_local_kfs(std::vector<int>& kfl, Marked marked, Mark mark);
-  // out: the local points of the keyframes kfl; gen: the generation of the list out holds, in
-  // and out (a list with an equal generation is equal element for element)
-  void collect_local_points(const std::vector<int>& kfl, std::vector<int>& out, long& gen);
-  void walk_local_points(const std::vector<int>& kfl, std::vector<int>& out);
-  // The structure epoch: bumped by every edit of what walk_local_points and expand_local_kfs
-  // read, so a point list built at this epoch from an equal keyframe list is still the list a
-  // walk would build.  The mutators (a missed one is the one way the cache below can be wrong):
-  //  * KFrame::mps entries of a stored keyframe: kf_set_mp, the only writer (set_bad, replace,
-  //    fuse_apply, local_bundle_adjustment's erasures, initialize, create_new_keyframe,
-  //    create_new_map_points); new_keyframe, which stores the frame's table whole;
-  //  * a point's bad flag: mark_bad, the only writer (set_bad, replace);
-  //  * a keyframe's bad flag, parent and children: kf_set_bad, update_connections;
-  //  * KFrame::ordered: update_best_covisibles (add_connection, erase_connection),
-  //    update_connections, kf_set_bad;
-  //  * reset and initialize.
-  // Temporary (VO) points (handles >= kTemp) are never in a keyframe and need no epoch.
-  long struct_epoch_ = 0;
-  void kf_set_mp(int kf, int idx, int h) {
-    kfs_[kf].mps[idx] = h;
-    struct_epoch_++;
-  }
-  // The keyframe list and point list of the last walks (copies: commit_local_map swaps the
-  // vectors the callers hold), each list's generation and the epoch they were built at (one for
-  // all: a structure edit drops every kept list).  MMT_LOCALMAP_CACHE:
-  // 1 (default) a call with an equal keyframe list at an unchanged epoch takes the cached points;
-  // 0 walks every time (A/B); 2 also walks on every hit and throws when the lists differ.
-  // MMT_LOCALMAP_CACHE_WAYS (1-8, default 4): that many lists of the current epoch are kept, the
-  // least recently used one replaced (the counted keyframe set flickers at its margin from frame
-  // to frame and comes back: §5h of DESIGN.md).
-  int lpc_mode_ = 1, lpc_ways_ = 4;
-  struct LpcEntry {
-    std::vector<int> kfs, pts;
-    long gen = 0, used = 0;
-    bool valid = false;
-  };
-  static constexpr int kLpcMaxWays = 8;
-  LpcEntry lpc_[kLpcMaxWays];
-  std::vector<int> lpc_check_;
-  long lpc_epoch_ = -1, lpc_tick_ = 0, lpc_hits_ = 0, lpc_rebuilds_ = 0, lpc_new_epoch_ = 0;
+  // the cache's collect for the two callers; throws when MMT_LOCALMAP_CACHE=2 finds a difference
+  void collect_checked(const std::vector<int>& kfl, std::vector<int>& out, long& gen);
   long ids_uploads_ = 0;
-  long list_gen_ = 0;                  // the last generation handed out
   long local_gen_ = 0, spec_gen_ = 0;  // the generations of localPts_ and spec_pts_
-  // compute_distinctive's pairwise descriptor distances of points with more than 32 good
-  // observations, by observation ((keyframe << 32) | key, keyframe order)
-  struct DistCache {
-    std::vector<uint64_t> ids;
-    std::vector<uint16_t> d;
-  };
-  std::unordered_map<int, DistCache> dcache_;
   void run_overlap() {
     if (!overlap_) return;
     std::function<void()> fn = std::move(overlap_);
     overlap_ = nullptr;
     fn();
   }
-  static constexpr int kTemp = 1 << 29;
-  MPoint& mp(int h) { return h >= kTemp ? temps_[h - kTemp] : pts_[h]; }
+  static constexpr int kTemp = MapGraph::kTemp;
   bool track_with_motion_model(MapFrameH& C, const GridFrame& G, float* Tcw, MapFrameH& L,
                                float* Tlast, const float* vel, MapStatsH& st);
   bool track_reference_subst(MapFrameH& C, const GridFrame& G, float* Tcw, const MapFrameH& L,
@@ -340,20 +198,8 @@ class MapEngine {
   void search_local_points(MapFrameH& C, const GridFrame& G, const float* Tcw);
   bool need_new_keyframe(const MapFrameH& C);
   void create_new_keyframe(MapFrameH& C, const float* Tcw);
-  int new_keyframe(const MapFrameH& C, const float* Tcw);
-  int new_point_kf(const float* pos, int kf);
-  void add_observation(int h, int kf, int idx);
-  void set_bad(int h);
-  void compute_distinctive(int h);
-  void update_normal_depth(int h);
-  void update_connections(int kf);
-  void add_connection(int kf, int other, int w);
-  void update_best_covisibles(int kf);
-  int tracked_map_points(int kf, int minObs);
   void process_new_keyframe(int kf);
   void map_point_culling(int kf);
-  void mark_dirty(int h);
-  void mark_bad(int h);  // mbBad, the map's point count, the per-frame scan record
   // ---- LocalMapping after ProcessNewKeyFrame / MapPointCulling (mmt_localmap.hip)
   void local_mapping(int kf);
   void search_in_neighbors(int kf);
@@ -362,11 +208,7 @@ class MapEngine {
   void fuse_apply(int kf, int h, int bestIdx, int bestDist);
   void local_bundle_adjustment(int kf);
   void keyframe_culling(int kf);
-  void replace(int h, int by);
-  void erase_observation(int h, int kf);
-  void kf_set_bad(int kf);
-  void erase_connection(int kf, int other);
-  void set_pose(int kf, const float* Tcw);
+  void kf_set_bad(int kf);  // the graph's, then the keyframe database's erase
   void kf_store_add(int kf);
   // ---- vocabulary path (mmt_bowmap.hip)
   void bow_launch(const uint8_t* d_desc, int n, hipStream_t st);
@@ -412,30 +254,11 @@ class MapEngine {
 
   MapCamH cam_;
   int kcap_ = 0;
-  // map points in fixed chunks: growing the array never moves the existing points (a vector's
-  // reallocation moved all of them, 100k points at a time, inside a keyframe's point creation)
-#ifdef MMT_PTS_VECTOR  // A/B build (tools/build_prof_lib.sh)
-  std::vector<MPoint> pts_;
-#else
-  ChunkArray<MPoint> pts_;
-#endif
-  std::vector<MPoint> temps_;
-  // the fields the per-frame local-map scans read, one compact record per real point (pts_ index):
-  // UpdateLocalPoints walks ~13k point references and SearchLocalPoints ~4.4k, at random, and a
-  // 12-byte record keeps them in cache where the 136-byte MPoint does not
-  struct PtHot {
-    int trackRef = 0;  // mnTrackReferenceForFrame
-    int lastSeen = 0;  // mnLastFrameSeen
-    uint8_t bad = 0;
-  };
-  std::vector<PtHot> hot_;
-  std::vector<KFrame> kfs_;
   int state_ = 0;
   long frameNextId_ = 0;
-  int kfNextId_ = 0;
   long lastKFFrameId_ = 0;
   int refKF_ = -1;
-  std::vector<int> localKFs_, localPts_, recent_, dirty_;
+  std::vector<int> localKFs_, localPts_, recent_;
   std::vector<std::pair<float, int>> far_;  // UpdateLastFrame's far keys (scratch)
   std::vector<uint32_t> sort_key_;  // CreateNewKeyFrame's depth sort (scratch)
   std::vector<int> sort_idx_, sort_tmp_;
@@ -451,7 +274,6 @@ class MapEngine {
   bool pending_ok_ = false;  // track() succeeded, track_finish() pending
   long lastRelocFrameId_ = 0;
   long curId_ = 0;
-  int n_good_ = 0;  // non-bad map points
   hipStream_t s_ = nullptr;
   // MMT_MAP_PROFILE=1: host wall time per stage of track(), printed to stderr at destruction
   bool prof_on_ = false;

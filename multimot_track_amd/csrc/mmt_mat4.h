@@ -1,8 +1,14 @@
 // multimot_track_amd/csrc/mmt_mat4.h -- the float cv::Mat helpers of the tracker's pose
 // bookkeeping, shared by host and device so the device-side motion-model matrix equals the host's
 // bit for bit (double accumulation, float result; contraction is off in both compilations).
+// Plain C++ outside hipcc (the map graph and its host test include it without the device headers).
 #pragma once
+#if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
+#define MMT_HD __host__ __device__
+#else
+#define MMT_HD
+#endif
 
 #include <cmath>
 #include <cstdint>
@@ -11,7 +17,7 @@
 namespace mmt {
 
 // cv::gemm, CV_32F: C = A B (4x4)
-__host__ __device__ inline void mat4_mul(const float* A, const float* B, float* C) {
+MMT_HD inline void mat4_mul(const float* A, const float* B, float* C) {
   float R[16];
   for (int r = 0; r < 4; r++)
     for (int c = 0; c < 4; c++) {
@@ -23,7 +29,7 @@ __host__ __device__ inline void mat4_mul(const float* A, const float* B, float* 
 }
 
 // Tracking::InvMatrix: [R^T, -R^T t]
-__host__ __device__ inline void inv_mat(const float* T, float* Ti) {
+MMT_HD inline void inv_mat(const float* T, float* Ti) {
   float R[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
   for (int r = 0; r < 3; r++)
     for (int c = 0; c < 3; c++) R[4 * r + c] = T[4 * c + r];
@@ -35,7 +41,7 @@ __host__ __device__ inline void inv_mat(const float* T, float* Ti) {
   for (int i = 0; i < 16; i++) Ti[i] = R[i];
 }
 
-__host__ __device__ inline void mat4_eye(float* T) {
+MMT_HD inline void mat4_eye(float* T) {
   for (int i = 0; i < 16; i++) T[i] = (i % 5 == 0) ? 1.f : 0.f;
 }
 

@@ -1,4 +1,4 @@
-"""The local point list cache of TrackLocalMap (mmt_map.hip collect_local_points): the list of
+"""The local point list cache of TrackLocalMap (LocalPointCache, mmt_mapgraph.h): the list of
 the last walk is handed out again while the keyframe list and the map's structure epoch are
 unchanged, and the points' handles stay on the device while the list does.
 
