@@ -63,6 +63,8 @@
  *                          (LoopClosing::ComputeSim3 LoopClosing.cc:276-303), a batch of solvers
  *   mmt_search_by_sim3  <- ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)
  *                          ORBmatcher.cc:1477-1701 (LoopClosing.cc:325)
+ *   mmt_optimize_sim3   <- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
+ *                          Optimizer.cc:3934-4129 (LoopClosing.cc:327), a batch of candidates
  *   mmt_destroy         <- System::Shutdown / delete
  */
 #ifndef MMT_H
@@ -638,6 +640,63 @@ int mmt_search_by_sim3(mmt_ctx* ctx, const mmt_match_frame* kf1,
                        const uint8_t* skip2, float s12, const float* R12, const float* t12,
                        float th, const int32_t* matched12_in, int32_t* match_out, int* n_found,
                        int32_t* cand1_out, int32_t* cand2_out);
+
+/* Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale) (Optimizer.cc:3934-4129;
+ * LoopClosing.cc:327 with th2 10), for a batch of independent candidates: one call serves every
+ * candidate of a ComputeSim3 round whose Sim3Solver returned a similarity.  At most 64 problems and
+ * 16384 correspondences per problem; the whole batch is one launch.
+ *
+ * A problem holds what the reference gathers per correspondence that passes :4000-4002, in
+ * vpMatches1 order (vnIndexEdge, the map back to vpMatches1, is the caller's): X1c / X2c = the two
+ * map points in their own cameras (R1w P3D1w + t1w, the float cv::Mat product), obs1 / obs2 = the
+ * undistorted keys, inv_sigma2_1 / 2 = mvInvLevelSigma2[octave], the two cameras, bFixScale, th2
+ * and gScm's constructor arguments (s12, R12 row-major, t12).  Everything is promoted to double.
+ *
+ * What runs is g2o's optimisation of the one free VertexSim3Expmap over two fixed-point edges per
+ * correspondence (e12 = obs1 - cam_map1(project(S12 X2c)), e21 = obs2 - cam_map2(project(S12^-1
+ * X1c)), information inv_sigma2 I, Huber delta sqrtf(th2) in both rounds): g2o's numeric Jacobian
+ * (central difference at 1e-9), Sim3's exponential update from the left, a dense 7 x 7 LDLT and
+ * OptimizationAlgorithmLevenberg inside ORB-SLAM2's SparseOptimizer::optimize.  optimize(5); every
+ * pair with e12.chi2() > th2 || e21.chi2() > th2 is removed (n_bad); with fewer than 10 pairs left
+ * the call returns 0 and leaves g2oS12 alone (second_round 0); otherwise optimize(n_bad > 0 ? 10 :
+ * 5) on the pairs left, the same test again, and g2oS12 receives the estimate.  chi2() reads the
+ * error of the last computeActiveErrors, which is the last trial's state.  No depth test: a point
+ * mapped to z = 0 gives a non-finite error, which counts as an inlier and makes the trial rejected.
+ *
+ * results[i]: n_inliers = the return value; n_bad; second_round; (s, R, t) = g2oS12 after the call
+ * (scale(), rotation().toRotationMatrix() row-major, translation()), the input promoted when
+ * second_round is 0; kept (n bytes) = vpMatches1 still non-null (pairs cleared by the first test
+ * stay cleared); chi2 (optional, n x 2) = e12 / e21 chi2() of every pair at the state of the last
+ * test that ran (the pairs removed after round 1 are evaluated there too, beyond the reference, so
+ * that kept can be checked against it); stats = iterations of round 1 / 2, LM trials of round 1 / 2
+ * (diagnostic).  n == 0: nothing runs.  Pins: DESIGN.md section 2. */
+typedef struct mmt_sim3_opt_problem {
+  int n;
+  const float* X1c;        /* n x 3 */
+  const float* X2c;        /* n x 3 */
+  const float* obs1;       /* n x 2: pKF1->mvKeysUn[i].pt  */
+  const float* obs2;       /* n x 2: pKF2->mvKeysUn[i2].pt */
+  const float* inv_sigma2_1;  /* n */
+  const float* inv_sigma2_2;  /* n */
+  float fx1, fy1, cx1, cy1;   /* pKF1->mK */
+  float fx2, fy2, cx2, cy2;   /* pKF2->mK */
+  int fix_scale;           /* bFixScale */
+  float th2;
+  float s12, R12[9], t12[3];  /* gScm's constructor arguments (LoopClosing.cc:327) */
+} mmt_sim3_opt_problem;
+
+typedef struct mmt_sim3_opt_result {
+  int n_inliers;
+  int n_bad;
+  int second_round;
+  double s, R[9], t[3];
+  uint8_t* kept;           /* n bytes */
+  double* chi2;            /* optional, n x 2 */
+  int stats[4];
+} mmt_sim3_opt_result;
+
+int mmt_optimize_sim3(mmt_ctx* ctx, int n_problems, const mmt_sim3_opt_problem* problems,
+                      mmt_sim3_opt_result* results);
 
 /* A keyframe as SearchForTriangulation reads it: mvKeysUn, mDescriptors, mvuRight (< 0: monocular),
  * mFeatVec, whether mvpMapPoints[i] holds a MapPoint, and Tcw (row-major). */

@@ -244,6 +244,24 @@ class MmtSim3Probe(ctypes.Structure):
                 ("flags", ctypes.c_void_p), ("T12", ctypes.c_void_p)]
 
 
+class MmtSim3OptProblem(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int)] + \
+               [(k, ctypes.c_void_p) for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1",
+                                               "inv_sigma2_2")] + \
+               [(k, ctypes.c_float) for k in ("fx1", "fy1", "cx1", "cy1", "fx2", "fy2", "cx2",
+                                              "cy2")] + \
+               [("fix_scale", ctypes.c_int), ("th2", ctypes.c_float), ("s12", ctypes.c_float),
+                ("R12", ctypes.c_float * 9), ("t12", ctypes.c_float * 3)]
+
+
+class MmtSim3OptResult(ctypes.Structure):
+    _fields_ = [("n_inliers", ctypes.c_int), ("n_bad", ctypes.c_int),
+                ("second_round", ctypes.c_int), ("s", ctypes.c_double),
+                ("R", ctypes.c_double * 9), ("t", ctypes.c_double * 3),
+                ("kept", ctypes.c_void_p), ("chi2", ctypes.c_void_p),
+                ("stats", ctypes.c_int * 4)]
+
+
 class MmtSftKeyFrame(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p),
                 ("uR", ctypes.c_void_p), ("has_mp", ctypes.c_void_p), ("fv", MmtFeatureVector),
@@ -350,6 +368,7 @@ def lib():
                                          ctypes.POINTER(MmtMatchFrame),
                                          ctypes.POINTER(MmtKeyFramePoints), vp, ctypes.c_float,
                                          vp, vp, ctypes.c_float, vp, vp, vp, vp, vp]
+        L.mmt_optimize_sim3.argtypes = [vp, i32, vp, vp]
         L.mmt_map_counters_read.argtypes = [vp, ctypes.POINTER(MmtMapCounters)]
         L.mmt_map_dump.argtypes = [vp, vp, ctypes.POINTER(MmtMapDumpArrays)]
         L.mmt_set_keyframe_culling_ratio.argtypes = [vp, ctypes.c_double]
@@ -876,6 +895,48 @@ class Context:
             ctypes.c_float(s12), _p(R), _p(t), ctypes.c_float(th), _p(m12), _p(match),
             ctypes.byref(nf), _p(c1), _p(c2)))
         return nf.value, match[:n1], c1[:n1], c2[:n2]
+
+    def optimize_sim3(self, problems):
+        """Optimizer::OptimizeSim3 for a batch of candidates, one launch.  problems: dicts(X1c, X2c
+        (n x 3, the matched points in their own cameras), obs1, obs2 (n x 2, the undistorted keys),
+        inv_sigma2_1, inv_sigma2_2 (n), K1, K2, fix_scale, s12, R12, t12 (the start)[, th2 10]).
+        Returns per problem dict(n_inliers, n_bad, second_round, s, R, t (float64; the input when
+        second_round is false), kept (n bools), chi2 (n x 2: e12 / e21 at the last tested state),
+        stats (iterations of round 1 / 2, trials of round 1 / 2))."""
+        ns = len(problems)
+        keep = []
+        P = (MmtSim3OptProblem * max(ns, 1))()
+        R = (MmtSim3OptResult * max(ns, 1))()
+        outs = []
+        for i, pr in enumerate(problems):
+            arrs = [np.ascontiguousarray(pr[k], np.float32)
+                    for k in ("X1c", "X2c", "obs1", "obs2", "inv_sigma2_1", "inv_sigma2_2")]
+            n = len(arrs[4])
+            if [a.size for a in arrs] != [3 * n, 3 * n, 2 * n, 2 * n, n, n]:
+                raise ValueError("a problem's arrays follow its correspondences")
+            keep += arrs
+            P[i].n = n
+            (P[i].X1c, P[i].X2c, P[i].obs1, P[i].obs2, P[i].inv_sigma2_1,
+             P[i].inv_sigma2_2) = [a.ctypes.data for a in arrs]
+            P[i].fx1, P[i].fy1, P[i].cx1, P[i].cy1 = pr["K1"]
+            P[i].fx2, P[i].fy2, P[i].cx2, P[i].cy2 = pr["K2"]
+            P[i].fix_scale = int(bool(pr["fix_scale"]))
+            P[i].th2 = pr.get("th2", 10.0)
+            P[i].s12 = float(pr["s12"])
+            P[i].R12[:] = np.asarray(pr["R12"], np.float32).reshape(9).tolist()
+            P[i].t12[:] = np.asarray(pr["t12"], np.float32).reshape(3).tolist()
+            kept = np.zeros(max(n, 1), np.uint8)
+            chi2 = np.zeros((max(n, 1), 2), np.float64)
+            R[i].kept, R[i].chi2 = kept.ctypes.data, chi2.ctypes.data
+            outs.append((n, kept, chi2))
+        self._check(lib().mmt_optimize_sim3(self._h, ns, ctypes.addressof(P),
+                                            ctypes.addressof(R)))
+        return [dict(n_inliers=R[i].n_inliers, n_bad=R[i].n_bad,
+                     second_round=bool(R[i].second_round), s=float(R[i].s),
+                     R=np.array(R[i].R[:], np.float64).reshape(3, 3),
+                     t=np.array(R[i].t[:], np.float64), kept=kept[:n].astype(bool),
+                     chi2=chi2[:n].copy(), stats=list(R[i].stats))
+                for i, (n, kept, chi2) in enumerate(outs)]
 
     def local_bundle_adjustment(self, P):
         """Optimizer::LocalBundleAdjustment's solve on a problem dict (keys T, fixed, X, pt, kf,

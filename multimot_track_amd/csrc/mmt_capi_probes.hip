@@ -18,6 +18,7 @@
 #include "mmt_match.h"
 #include "mmt_pnp.h"
 #include "mmt_sim3.h"
+#include "mmt_sim3opt.h"
 #include "mmt_track.h"
 
 using mmt::ArgError;
@@ -481,6 +482,15 @@ int mmt_sim3solver_iterate(mmt_ctx* ctx, int n_solvers, const mmt_sim3_problem* 
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     mmt::sim3solver_iterate_gpu(ctx->stream, n_solvers, problems, randi, n_draw_iters,
                                 n_iterations, states, results, probes);
+  });
+}
+
+int mmt_optimize_sim3(mmt_ctx* ctx, int n_problems, const mmt_sim3_opt_problem* problems,
+                      mmt_sim3_opt_result* results) {
+  if (!ctx || (n_problems > 0 && (!problems || !results))) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    mmt::sim3_optimize_gpu(ctx->stream, n_problems, problems, results);
   });
 }
 
