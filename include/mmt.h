@@ -248,6 +248,12 @@ typedef struct mmt_flow_problem {
 } mmt_flow_problem;
 int mmt_pose_flow_solve(mmt_ctx* ctx, const mmt_flow_problem* problem, float* pose_out,
                         int* stats_out /* iterations, inliers, status */);
+/* The same solve with the initial pose read from device memory (init_on_device != 0: the path of
+ * the tracker's ego solve queued behind PoseOptimization) and, optionally, the mean world
+ * position of the solve's points (centre_out: 3 floats or null). */
+int mmt_pose_flow_solve_init_dev(mmt_ctx* ctx, const mmt_flow_problem* problem,
+                                 int init_on_device, float* pose_out, int* stats_out,
+                                 float* centre_out);
 
 /* Optimizer::PoseOptimization(Frame*) (reference include/Optimizer.h:43, src/Optimizer.cc:3121-3339)
  * on the frame's MapPoint observations (the edges of the frame's non-null mvpMapPoints, in index

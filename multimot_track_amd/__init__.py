@@ -587,6 +587,32 @@ class Context:
         self._check(lib().mmt_pose_flow_solve(self._h, ctypes.byref(pr), _p(pose), _p(st)))
         return int(st[2]), pose.reshape(4, 4), dict(iterations=int(st[0]), inliers=int(st[1]))
 
+    def flow_solve_init_dev(self, obs, flow, depth, tcw_last, init, rp_thres, prior_info,
+                            max_iters, K, init_on_device, use_noise=False, g0=0.0):
+        """flow_solve with the initial pose read from device memory (init_on_device) or by value:
+        (status, pose 4x4, stats, centre of the solve's points)."""
+        obs = np.ascontiguousarray(obs, np.float32)
+        flow = np.ascontiguousarray(flow, np.float32)
+        depth = np.ascontiguousarray(depth, np.float32)
+        pr = MmtFlowProblem()
+        pr.n = len(depth)
+        pr.obs, pr.flow, pr.depth = obs.ctypes.data, flow.ctypes.data, depth.ctypes.data
+        pr.Tcw_last[:] = np.asarray(tcw_last, np.float32).reshape(16).tolist()
+        pr.init[:] = np.asarray(init, np.float32).reshape(16).tolist()
+        pr.rp_thres, pr.prior_info, pr.max_iters = rp_thres, prior_info, max_iters
+        pr.use_noise, pr.g0 = int(use_noise), g0
+        pr.fx, pr.fy, pr.cx, pr.cy = K
+        pose = np.zeros(16, np.float32)
+        st = np.zeros(3, np.int32)
+        centre = np.zeros(3, np.float32)
+        fn = lib().mmt_pose_flow_solve_init_dev
+        fn.argtypes = [ctypes.c_void_p, ctypes.POINTER(MmtFlowProblem), ctypes.c_int32,
+                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self._check(fn(self._h, ctypes.byref(pr), int(init_on_device), _p(pose), _p(st),
+                       _p(centre)))
+        return (int(st[2]), pose.reshape(4, 4), dict(iterations=int(st[0]), inliers=int(st[1])),
+                centre)
+
     def pose_optimization(self, Xw, obs, inv_sigma2, tcw, K, bf):
         """Optimizer::PoseOptimization (D1): (n_inliers, pose 4x4, mvbOutlier flags)."""
         Xw = np.ascontiguousarray(Xw, np.float32)

@@ -172,15 +172,17 @@ static void check_sft_keyframe(const mmt_sft_keyframe* k) {
 
 extern "C" {
 
-int mmt_pose_flow_solve(mmt_ctx* ctx, const mmt_flow_problem* pr, float* pose_out,
-                        int* stats_out) {
+// init_on_device: the initial pose goes to device memory and the descriptor names it (init_dev),
+// its by-value copy poisoned; centre_out (3 floats, optional): ObjCentre3D_pre
+static int flow_solve_probe(mmt_ctx* ctx, const mmt_flow_problem* pr, bool init_on_device,
+                            float* pose_out, int* stats_out, float* centre_out) {
   if (!ctx || !pr || !pose_out || !stats_out || pr->n < 0) return MMT_EINVAL;
   return guard(ctx, [&] {
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     hipStream_t s = ctx->stream;
     const int n = pr->n, cap = std::max(n, 1);
     DevBuf<float2> obs(cap), flow(cap);
-    DevBuf<float> depth(cap), pose(16);
+    DevBuf<float> depth(cap), pose(16), init(16), centre(3);
     DevBuf<double> scratch(mmt::flow_scratch_doubles(cap));
     DevBuf<int> st(3);
     DevBuf<mmt::FlowSolveDesc> dd(1);
@@ -211,6 +213,12 @@ int mmt_pose_flow_solve(mmt_ctx* ctx, const mmt_flow_problem* pr, float* pose_ou
     d.stats = st.p;
     d.gx = gx.p;
     d.gx_seq = 1;
+    if (centre_out) d.centre_out = centre.p;
+    if (init_on_device) {
+      init.up(pr->init, 16, s);
+      d.init_dev = init.p;
+      memset(d.init, 0xFF, sizeof(d.init));  // NaNs: a solve that read them would show
+    }
     dd.up(&d, 1, s);
     pose.up(pr->init, 16, s);
     if (groups > 1)
@@ -219,10 +227,21 @@ int mmt_pose_flow_solve(mmt_ctx* ctx, const mmt_flow_problem* pr, float* pose_ou
       mmt::launch_flow_lm(dd.p, 1, n, s);
     pose.down(pose_out, 16, s);
     st.down(stats_out, 3, s);
+    if (centre_out) centre.down(centre_out, 3, s);
     MMT_HIP(hipStreamSynchronize(s));
     if (stats_out[2] == 2)
       throw mmt::DeviceError("pose flow solve: the split solve's workgroups were not resident together");
   });
+}
+
+int mmt_pose_flow_solve(mmt_ctx* ctx, const mmt_flow_problem* pr, float* pose_out,
+                        int* stats_out) {
+  return flow_solve_probe(ctx, pr, false, pose_out, stats_out, nullptr);
+}
+
+int mmt_pose_flow_solve_init_dev(mmt_ctx* ctx, const mmt_flow_problem* pr, int init_on_device,
+                                 float* pose_out, int* stats_out, float* centre_out) {
+  return flow_solve_probe(ctx, pr, init_on_device != 0, pose_out, stats_out, centre_out);
 }
 
 int mmt_pose_optimization(mmt_ctx* ctx, const mmt_pose_opt_problem* pr, float* pose_out,

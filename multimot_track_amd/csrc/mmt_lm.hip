@@ -740,7 +740,7 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
   double RB[12];
   // The LM bookkeeping below is computed redundantly by every thread from the block sums in LDS
   // (identical inputs, identical results), so only the 6x6 solve needs a lane-0 section.
-  DSE3 P = dse3_from_float(D.init);
+  DSE3 P = dse3_from_float(D.init_dev ? D.init_dev : D.init);
   const double hin = kInfo + c.pinfo;  // h of every edge when none is Huber-active
   // the sums of the current system (vc): sum k in lane k of every wave
   // ---- initial linearisation (computeActiveErrors + buildSystem at the initial estimate)

@@ -123,6 +123,17 @@ class MapEngine {
   // beside the ego solve.  Returns whether it is still pending (track() ran no chain).
   void set_overlap(std::function<void()> fn) { overlap_ = std::move(fn); }
   bool overlap_pending() const { return (bool)overlap_; }
+  // called by TrackLocalMap's chain (C3 + D1) once D1 and the copies of its results are enqueued
+  // and an event behind them is recorded, with the device address of D1's pose (16 floats; always
+  // the pose track() returns when this chain is the frame's last: D1 copies its input below 3
+  // edges): what it enqueues on the stream runs behind D1 without a host round trip, and the host
+  // waits for the event only.  The tracker queues the flow solve (D2) here.
+  void set_after_d1(std::function<void(const float*)> fn) { after_d1_ = std::move(fn); }
+  // D2 launches by kind (0 queued behind D1, 1 launched by the host, 2 queued and then redone by
+  // the host because the pose differed), for the profile line
+  void count_d2(int kind) { d2_count_[kind]++; }
+  void set_d2_chain_mode(int m) { d2_chain_mode_ = m; }
+  const float* d1_pose_host() const { return h_pose_; }  // the last chain's D1 pose, as copied
   // end of Track: mlRelativeFramePoses.push_back(Tcw * Tref^-1) (Tracking.cc:2481-2489)
   void frame_done(const MapFrameH& C, const float* Tcw);
   int state() const { return state_; }
@@ -177,6 +188,10 @@ class MapEngine {
   void collect_checked(const std::vector<int>& kfl, std::vector<int>& out, long& gen);
   long ids_uploads_ = 0;
   long local_gen_ = 0, spec_gen_ = 0;  // the generations of localPts_ and spec_pts_
+  std::function<void(const float*)> after_d1_;
+  hipEvent_t ev_d1_ = nullptr;
+  long d2_count_[3] = {0, 0, 0};
+  int d2_chain_mode_ = 1;
   void run_overlap() {
     if (!overlap_) return;
     std::function<void()> fn = std::move(overlap_);

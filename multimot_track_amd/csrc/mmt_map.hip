@@ -60,10 +60,12 @@ MapEngine::~MapEngine() {
     fprintf(stderr, "[mmt map profile] per frame: %.1f local keyframes, %.1f local points, "
             "%.1f C3 edges; %zu map points allocated, %d keyframes at the end; local map "
             "speculated %ld times, taken %ld; local point list cache (MMT_LOCALMAP_CACHE=%d) "
-            "hits %ld, rebuilds %ld (%ld of them after a structure edit, %ld ids uploads)\n",
+            "hits %ld, rebuilds %ld (%ld of them after a structure edit, %ld ids uploads); flow "
+            "solves (MMT_D2_CHAIN=%d) chained %ld, host-launched %ld, redone %ld\n",
             prof_cnt_[0] / prof_n_, prof_cnt_[1] / prof_n_, prof_cnt_[2] / prof_n_, graph_.n_points(),
             n_keyframes(), spec_tries_, spec_hits_, lpc_.mode(), lpc_.hits(), lpc_.rebuilds(),
-            lpc_.epoch_rebuilds(), ids_uploads_);
+            lpc_.epoch_rebuilds(), ids_uploads_, d2_chain_mode_, d2_count_[0], d2_count_[1],
+            d2_count_[2]);
   }
   if (s_) (void)hipStreamSynchronize(s_);
   if (lm_s_) {
@@ -71,6 +73,7 @@ MapEngine::~MapEngine() {
     (void)hipStreamDestroy(lm_s_);
   }
   if (ev_early_) (void)hipEventDestroy(ev_early_);
+  if (ev_d1_) (void)hipEventDestroy(ev_d1_);
   for (void* p : dallocs_) (void)hipFree(p);
   for (void* p : hallocs_) (void)hipHostFree(p);
 }
@@ -131,6 +134,7 @@ void MapEngine::setup(const MapCamH& cam, int kcap) {
   graph_.setup(cam_.scale, cam_.nlevels, prof_on_);
   h_early_ = pinned<uint8_t>(kOutHdr + 4 * (size_t)kcap);
   MMT_HIP(hipEventCreateWithFlags(&ev_early_, hipEventDisableTiming));
+  MMT_HIP(hipEventCreateWithFlags(&ev_d1_, hipEventDisableTiming));
   // LocalMapping's stream, normal priority (high / low measured within noise / slower in round 5,
   // without the vocabulary): its kernels (keyframe store copies, the BoW transform, Fuse,
   // SearchForTriangulation, the local BA) need nothing of the frame's flow solve.  MMT_LM_PRIO=high
@@ -839,8 +843,16 @@ void MapEngine::search_local_points(MapFrameH& C, const GridFrame& G, const floa
   launch_pose_opt(d_pod_, 1, std::min(C.n, nbase + m), s_);
   MMT_HIP(hipMemcpyAsync(h_out_, d_out_, out_bytes(C.n), hipMemcpyDeviceToHost, s_));
   if (m > 0) MMT_HIP(hipMemcpyAsync(h_inview_, d_inview_, (size_t)m, hipMemcpyDeviceToHost, s_));
+  // what the hook enqueues (the flow solve) runs behind D1; the host waits for D1's results only
+  if (after_d1_) {
+    MMT_HIP(hipEventRecord(ev_d1_, s_));
+    after_d1_(d_pose_);
+  }
   run_overlap();
-  MMT_HIP(hipStreamSynchronize(s_));
+  if (after_d1_)
+    MMT_HIP(hipEventSynchronize(ev_d1_));
+  else
+    MMT_HIP(hipStreamSynchronize(s_));
   // IncreaseVisible for the points in view (mbTrackInView itself is read by the GPU search only,
   // from h_inview_: the host's copy of the flag is not kept, so only the points in view are touched)
   for (int j = 0; j < m; j++)

@@ -99,6 +99,9 @@ struct FlowSolveDesc {
   // spin bound of the exchange waits in 100 MHz wall-clock ticks (0: 0.1 s); a test hook shortens
   // it to force the not-resident status
   unsigned long long gx_spin;
+  // optional: the initial pose (16 floats) in device memory, read instead of `init` by every
+  // workgroup; a solve queued behind the kernel that writes the pose needs no host round trip
+  const float* init_dev;
 };
 
 // A large single solve split over up to kFlowSplitMax workgroups (one slice of the edges each),

@@ -149,6 +149,7 @@ class Tracker {
   T* alloc(size_t n);
   // ego part of a frame: samples, hand-off, D2 launched on `st` (no wait)
   void ego_launch(const FrameArgs& a, FrameOut& out, hipStream_t st);
+  void enqueue_d2(const float* init_dev, hipStream_t st);
   // waits for the ego solve, updates the motion model, queues the frame's object path
   void ego_map_finish(FrameOut& out);
   void ego_finish(FrameOut& out, hipStream_t st);
@@ -209,6 +210,9 @@ class Tracker {
     int n_static[3];
   };
   bool ego_pending_ = false;
+  bool d2_chain_ = true;    // MMT_D2_CHAIN
+  bool d2_queued_ = false;  // this frame's TrackLocalMap chain queued the flow solve
+  hipStream_t ego_st_ = nullptr;
   float ego_Tinit_[16];
   EgoHost* eh_ = nullptr;
   ObjFrame qa_;                  // ego done, object path not yet enqueued

@@ -356,6 +356,15 @@ void Tracker::setup(const mmt_config& cfg, OrbEngine* engine, int max_chunk) {
   // MMT_DEBUG_SPLIT_SPIN: the split ego solve's exchange spin bound in wall-clock ticks (test
   // hook: a tiny bound forces the not-resident status and so the one-workgroup re-run)
   if (const char* ss = getenv("MMT_DEBUG_SPLIT_SPIN")) split_spin_ = strtoull(ss, nullptr, 10);
+  // The flow solve queued behind TrackLocalMap's D1, its initial pose read on the device
+  // (MMT_D2_CHAIN=0: launched by the host once it has the pose, as before; A/B)
+  if (const char* e = getenv("MMT_D2_CHAIN")) d2_chain_ = atoi(e) != 0;
+  map_.set_d2_chain_mode(d2_chain_ ? 1 : 0);
+  if (d2_chain_)
+    map_.set_after_d1([this](const float* d_pose) {
+      enqueue_d2(d_pose, ego_st_);
+      d2_queued_ = true;
+    });
 }
 
 void Tracker::reset() {
@@ -650,6 +659,8 @@ void Tracker::ego_launch(const FrameArgs& a, FrameOut& out, hipStream_t st) {
     // medians of 5, profiles/r06_ab_overlap_c3.txt), else the first chain (splitting it over the
     // two chains measured slower in round 4: 888 against 903 frames/s)
     map_.set_overlap([this] { obj_advance(); });
+    ego_st_ = st;
+    d2_queued_ = false;
     const int rr = map_.track(C.m, G, ego_Tinit_, Ls.m, Ls.Tview, V_, hasVelocity_,
                               bSecondFrame_, ms, st);
     map_.set_overlap(nullptr);  // not taken (no chain ran): the loop runs it
@@ -665,7 +676,29 @@ void Tracker::ego_launch(const FrameArgs& a, FrameOut& out, hipStream_t st) {
     map_finish_pending_ = true;
   }
   C.bSecond = bSecondFrame_;
-  // ---- D2 (PoseOptimizationFlow2Cam)
+  // ---- D2 (PoseOptimizationFlow2Cam): queued behind TrackLocalMap's D1 when that chain ran and
+  // its pose is the one the branch ended with (the 64 bytes compared); else launched from here
+  if (d2_queued_ && memcmp(ego_Tinit_, map_.d1_pose_host(), sizeof(ego_Tinit_)) == 0) {
+    map_.count_d2(0);
+  } else {
+    if (d2_queued_) {
+      // not expected: the queued solve started from another pose.  Its descriptor upload reads
+      // eh_->d2, so it must have run before the descriptor is rewritten
+      MMT_HIP(hipStreamSynchronize(st));
+      map_.count_d2(2);
+    } else {
+      map_.count_d2(1);
+    }
+    enqueue_d2(nullptr, st);
+  }
+  ego_pending_ = true;
+}
+
+// The ego flow solve on `st`: descriptor upload, the granule reset when the salt wraps, the solve
+// and the copy of its result.  init_dev: the initial pose in device memory (written by work
+// enqueued before this), else ego_Tinit_.  mLastFrame's pose must be final (UpdateLastFrame).
+void Tracker::enqueue_d2(const float* init_dev, hipStream_t st) {
+  FrameSlot& Ls = slot_[last_];
   FlowSolveDesc& d2 = eh_->d2;  // pinned: the upload below stays asynchronous
   memset(&d2, 0, sizeof(d2));
   d2.d_n = Ls.st.count;
@@ -674,7 +707,10 @@ void Tracker::ego_launch(const FrameArgs& a, FrameOut& out, hipStream_t st) {
   d2.flow = Ls.st.flow;
   d2.depth = Ls.st.depth;
   memcpy(d2.Tcw_last, Ls.Tview, sizeof(d2.Tcw_last));
-  memcpy(d2.init, ego_Tinit_, sizeof(d2.init));
+  if (init_dev)
+    d2.init_dev = init_dev;
+  else
+    memcpy(d2.init, ego_Tinit_, sizeof(d2.init));
   d2.rp_thres = 0.04f;
   d2.use_noise = 1;
   d2.g0 = g0_;
@@ -702,7 +738,6 @@ void Tracker::ego_launch(const FrameArgs& a, FrameOut& out, hipStream_t st) {
     launch_flow_lm(d_descs_, 1, eh_->n_static[last_], st);
   MMT_HIP(hipMemcpyAsync(eh_->Tcw, d_poses_, sizeof(eh_->Tcw) + sizeof(eh_->st),
                          hipMemcpyDeviceToHost, st));
-  ego_pending_ = true;
 }
 
 // The map branch's host-only tail (keyframe decision and creation) while D2 runs on the GPU.

@@ -43,8 +43,39 @@ for chain, mk in markers.items():
     for n, d in sorted(dur.items(), key=lambda kv: -kv[1])[:12]:
         print("    %-24s %8.1f us per frame" % (n, d / frames / 1e3))
 
-# interference: ego kernels' durations by what ran beside them on the other queues
 ego_q = next((q for s, e, q, n in ks if n == "k_flow_lm_split"), None)
+
+# the ego queue's two host-bound gaps per frame: the end of the C2 chain's D1 (k_pose_opt after
+# k_sbp_frame) to the start of k_local_cand, and the end of the C3 chain's D1 (k_pose_opt after
+# k_local_cand) to the start of the flow solve
+if ego_q is not None:
+    gaps = {"C3 D1 end -> k_flow_lm_split": [], "C2 D1 end -> k_local_cand": []}
+    chain, d1 = None, None
+    for s, e, q, n in ks:
+        if q != ego_q:
+            continue
+        if n.startswith("k_sbp_frame"):
+            chain, d1 = "C2", None
+        elif n.startswith("k_local_cand"):
+            if d1 is not None and d1[0] == "C2":
+                gaps["C2 D1 end -> k_local_cand"].append(s - d1[1])
+            chain, d1 = "C3", None
+        elif n.startswith("k_pose_opt") and chain is not None:
+            d1 = (chain, e)
+        elif n == "k_flow_lm_split":
+            if d1 is not None and d1[0] == "C3":
+                gaps["C3 D1 end -> k_flow_lm_split"].append(s - d1[1])
+            chain, d1 = None, None
+    for k, v in gaps.items():
+        if len(v) < 10:
+            print("gap %s: seen %d times: skipped" % (k, len(v)))
+            continue
+        v = sorted(v[len(v) // 10:])  # the first tenth: the map is still small
+        print("gap %-30s median %6.1f us, p90 %6.1f us, mean %6.1f us over %d frames" % (
+            k, statistics.median(v) / 1e3, v[int(0.9 * (len(v) - 1))] / 1e3,
+            statistics.mean(v) / 1e3, len(v)))
+
+# interference: ego kernels' durations by what ran beside them on the other queues
 if ego_q is not None:
     others = [(s, e, n) for s, e, q, n in ks if q != ego_q and "copy" not in n]
     for target in ("k_pose_opt_l<2>", "k_match_fix", "k_flow_lm_split"):
