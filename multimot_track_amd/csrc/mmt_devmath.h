@@ -171,97 +171,6 @@ __device__ inline DSE3 dse3_mul(const DSE3& a, const DSE3& b) {
   return r;
 }
 
-// 6x6 LDLT with symmetric diagonal pivoting on the LOWER triangle (Eigen LDLT<MatrixXd>); returns
-// false when not positive (LDLT::isPositive()).  Every array index is a compile-time constant
-// (pivot swaps by predicated unrolled blocks), so the factorisation stays in registers.
-__device__ inline bool ldlt_solve6(const double (&Hl)[36], const double (&b)[6], double (&x)[6]) {
-  double A[6][6], L[6][6], D[6];
-  int perm[6] = {0, 1, 2, 3, 4, 5};
-#pragma unroll
-  for (int r = 0; r < 6; r++)
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-      A[r][c] = (c <= r) ? Hl[6 * r + c] : Hl[6 * c + r];
-      L[r][c] = 0.0;
-    }
-  bool positive = true;
-#pragma unroll
-  for (int k = 0; k < 6; k++) {
-    int p = k;
-    double best = fabs(A[k][k]);
-#pragma unroll
-    for (int i = k + 1; i < 6; i++)
-      if (fabs(A[i][i]) > best) {
-        best = fabs(A[i][i]);
-        p = i;
-      }
-#pragma unroll
-    for (int i = k + 1; i < 6; i++)
-      if (p == i) {
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          const double t = A[k][c];
-          A[k][c] = A[i][c];
-          A[i][c] = t;
-        }
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-          const double t = A[r][k];
-          A[r][k] = A[r][i];
-          A[r][i] = t;
-        }
-#pragma unroll
-        for (int c = 0; c < k; c++) {
-          const double t = L[k][c];
-          L[k][c] = L[i][c];
-          L[i][c] = t;
-        }
-        const int t = perm[k];
-        perm[k] = perm[i];
-        perm[i] = t;
-      }
-    double d = A[k][k];
-#pragma unroll
-    for (int c = 0; c < k; c++) d -= L[k][c] * L[k][c] * D[c];
-    D[k] = d;
-    if (d < 0) positive = false;
-#pragma unroll
-    for (int i = k + 1; i < 6; i++) {
-      double s = A[i][k];
-#pragma unroll
-      for (int c = 0; c < k; c++) s -= L[i][c] * L[k][c] * D[c];
-      L[i][k] = (d != 0) ? s / d : 0.0;
-    }
-    L[k][k] = 1.0;
-  }
-  if (!positive) return false;
-  double y[6];
-#pragma unroll
-  for (int i = 0; i < 6; i++) {
-    double v = 0;
-#pragma unroll
-    for (int j = 0; j < 6; j++)
-      if (perm[i] == j) v = b[j];
-    y[i] = v;
-  }
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int c = 0; c < i; c++) y[i] -= L[i][c] * y[c];
-#pragma unroll
-  for (int i = 0; i < 6; i++) y[i] = (D[i] != 0) ? y[i] / D[i] : 0.0;
-#pragma unroll
-  for (int i = 5; i >= 0; i--)
-#pragma unroll
-    for (int r = i + 1; r < 6; r++) y[i] -= L[r][i] * y[r];
-#pragma unroll
-  for (int i = 0; i < 6; i++)
-#pragma unroll
-    for (int j = 0; j < 6; j++)
-      if (perm[i] == j) x[j] = y[i];
-  return true;
-}
-
 // Block sum of K <= 32 doubles held per thread (blockDim a multiple of 64): a butterfly
 // reduce-scatter inside each wave (32 shuffles instead of 6 per value), then one LDS pass across
 // waves.  `red` holds 32 doubles per wave; the sums land in out[0..K) (LDS), visible to every

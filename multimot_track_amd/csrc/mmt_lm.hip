@@ -15,14 +15,25 @@
 // scratch arrays).  An LM trial is
 //   Schur pass   J^T W J terms of the Schur complement (27 sums; only when some edge is
 //                Huber-active, otherwise closed form from the current system's sums)
-//   6x6 solve    computed redundantly by every thread from the sums
-//   pass 1       flow back-substitution and the trial's errors: chi2 and the scale term (2 sums)
-//   pass 2       accepted trials only: the flow step and the linearisation at the new state
-//                (H, b and the closed-form Schur sums: 63 sums), the next trial's system
-// so a rejected trial costs one light pass and a DPP reduction of two sums.  The 63-sum reductions
-// go through an LDS transpose tile (mmt_devmath.h: block_sum_tile_lanes).  Sums are reduced in a
-// different order than the CPU checker's sequential loops, so poses agree to rounding (1e-4 bar),
-// not bit for bit.
+//   6x6 solve    computed redundantly by every thread from the sums (on a clean system for the
+//                next four lambdas of a rejection chain at once: the candidate table)
+//   trial pass   one of two forms, fixed per instantiation of flow_lm_body<IR, SPLIT>:
+//     fused      flow back-substitution, the trial's errors and the linearisation at the trial
+//                state in one pass and one 63-sum reduction ([0] chi2, [1] the scale term, the
+//                rest H, b and the closed-form Schur sums of the next system); an accepted trial
+//                adopts the pending state, a rejected one discards it
+//     two-pass   pass 1: back-substitution and errors, chi2 and the scale term (2 sums, DPP);
+//                pass 2, accepted trials only: the flow step and the 63-sum linearisation.  A
+//                rejected trial costs the light pass only
+//   <1, false>   k_flow_lm, N <= threads: fused, the 63 sums reduced in registers
+//                (mmt_devmath.h: block_sum_regs64)
+//   <1, true>    k_flow_lm_split, slice <= threads: the same, then one exchange
+//   <2, false>   k_flow_lm, N > 256: two-pass, the 63 sums through an LDS transpose tile
+//                (block_sum_tile_lanes); edges from 512 on in the global item arrays
+//   <2, true>    k_flow_lm_split, slice > 256: fused through the tile when every slice of the
+//                solve has at most 512 edges, two-pass (an exchange per pass) otherwise
+// Sums are reduced in a different order than the CPU checker's sequential loops, so poses agree
+// to rounding (1e-4 bar), not bit for bit.
 
 #include <hip/hip_runtime.h>
 
@@ -369,40 +380,49 @@ __device__ __forceinline__ void schur_terms(const Cam& c, const DSE3& P, const L
   }
 }
 
-// pass 1 of a trial: back-substitution of the flow increment (when the 6x6 solve succeeded) and
-// the errors at the trial state (PN, f + xl), accumulated into s_chi (the trial chi2 term) and
-// s_sc (the scale term)
+// flow back-substitution of one correspondence after a successful 6x6 solve: the flow increment
+// xl from the pose increment xb.  Bcur: w J at P, kept from the linearisation that built the
+// current system (register item 0 of every thread); null for the second register item and the
+// global items, which project again.
+__device__ __forceinline__ void back_substitute(const Cam& c, const DSE3& P, LMItem& it, int i,
+                                                double lam, double ilam, const double* xb,
+                                                const double* Bcur) {
+  const double bl0 = it.bl[0], bl1 = it.bl[1];
+  const double w = it.w, h = w + c.pinfo;
+  double c0 = bl0, c1 = bl1;
+  if (Bcur) {
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      c0 -= Bcur[a] * xb[a];
+      c1 -= Bcur[6 + a] * xb[a];
+    }
+  } else {
+    double x, y, z;
+    map(P, it.X, x, y, z);
+    double J[2][6];
+    jac(x, y, drcp(z), c.fx, c.fy, J);
+#pragma unroll
+    for (int a = 0; a < 6; a++) {
+      c0 -= w * J[0][a] * xb[a];
+      c1 -= w * J[1][a] * xb[a];
+    }
+  }
+  const double ihl = drcp(h + lam);
+  double xl0 = c0 * ihl - h * c1 * ihl * ilam;
+  if (i > 0) xl0 += c0 * ilam;  // stride-2 spill of landmark i-1's third Dinv row
+  it.xl[0] = xl0;
+  it.xl[1] = c1 * ilam;
+}
+
+// pass 1 of the two-pass trial: back-substitution of the flow increment (when the 6x6 solve
+// succeeded) and the errors at the trial state (PN, f + xl), accumulated into s_chi (the trial
+// chi2 term) and s_sc (the scale term)
 __device__ __forceinline__ void trial_terms(const Cam& c, const DSE3& P, const DSE3& PN,
                                             LMItem& it, int i, bool ok2, double lam, double ilam,
                                             const double* xb, double& s_chi, double& s_sc,
                                             const double* Bcur = nullptr) {
   const double bl0 = it.bl[0], bl1 = it.bl[1];
-  if (ok2) {
-    const double w = it.w, h = w + c.pinfo;
-    double c0 = bl0, c1 = bl1;
-    if (Bcur) {  // w J at P, kept from the linearisation that built the current system
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-        c0 -= Bcur[a] * xb[a];
-        c1 -= Bcur[6 + a] * xb[a];
-      }
-    } else {
-      double x, y, z;
-      map(P, it.X, x, y, z);
-      double J[2][6];
-      jac(x, y, drcp(z), c.fx, c.fy, J);
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-        c0 -= w * J[0][a] * xb[a];
-        c1 -= w * J[1][a] * xb[a];
-      }
-    }
-    const double ihl = drcp(h + lam);
-    double xl0 = c0 * ihl - h * c1 * ihl * ilam;
-    if (i > 0) xl0 += c0 * ilam;  // stride-2 spill of landmark i-1's third Dinv row
-    it.xl[0] = xl0;
-    it.xl[1] = c1 * ilam;
-  }
+  if (ok2) back_substitute(c, P, it, i, lam, ilam, xb, Bcur);
   const double xl0 = it.xl[0], xl1 = it.xl[1];
   const double f0 = it.f[0] + xl0, f1 = it.f[1] + xl1;
   double x, y, z;
@@ -421,8 +441,8 @@ __device__ __forceinline__ void trial_terms(const Cam& c, const DSE3& P, const D
   s_sc += xl0 * (lam * xl0 + bl0) + xl1 * (lam * xl1 + bl1);
 }
 
-// pass 2 (accepted trials only): the flow step is taken and the edge linearised at the new state
-// (PN, f + xl), which builds the next iteration's system
+// pass 2 of the two-pass trial (accepted trials only): the flow step is taken and the edge
+// linearised at the new state (PN, f + xl), which builds the next iteration's system
 template <bool FIRST>
 __device__ __forceinline__ void accept_terms(const Cam& c, const DSE3& PN, LMItem& it, double* row,
                                              double* Bnext = nullptr) {
@@ -433,44 +453,19 @@ __device__ __forceinline__ void accept_terms(const Cam& c, const DSE3& PN, LMIte
                    it.bl[1], mh, Bnext);
 }
 
-// the split solve's fused trial pass: back-substitution and errors as trial_terms, and the
-// linearisation at the trial state (PN, f + xl) as the accepted trial's pass 2 would compute it,
-// into the tile row: [0] the trial's chi2 term, [1] its scale term, the rest the system the next
-// trial uses if this one is accepted.  The new robust weight, landmark gradient and w J stay
+// the fused trial pass: back-substitution and errors as trial_terms, and the linearisation at the
+// trial state (PN, f + xl) as pass 2 would compute it, into `row` (the thread's tile row, or its
+// 64 sums in registers): [0] the trial's chi2 term, [1] its scale term, the rest the system the
+// next trial uses if this one is accepted.  The new robust weight, landmark gradient and w J stay
 // pending (pw, pb, Bnext) until the decision; f, w and bl of the item are untouched.
 template <bool FIRST>
-__device__ __forceinline__ void spec_terms(const Cam& c, const DSE3& P, const DSE3& PN, LMItem& it,
-                                           int i, bool ok2, double lam, double ilam,
-                                           const double* xb, double* row, double& pw,
-                                           double& pb0, double& pb1, const double* Bcur,
-                                           double* Bnext) {
+__device__ __forceinline__ void fused_terms(const Cam& c, const DSE3& P, const DSE3& PN, LMItem& it,
+                                            int i, bool ok2, double lam, double ilam,
+                                            const double* xb, double* row, double& pw,
+                                            double& pb0, double& pb1, const double* Bcur,
+                                            double* Bnext) {
   const double bl0 = it.bl[0], bl1 = it.bl[1];
-  if (ok2) {
-    const double w = it.w, h = w + c.pinfo;
-    double c0 = bl0, c1 = bl1;
-    if (Bcur) {
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-        c0 -= Bcur[a] * xb[a];
-        c1 -= Bcur[6 + a] * xb[a];
-      }
-    } else {
-      double x, y, z;
-      map(P, it.X, x, y, z);
-      double J[2][6];
-      jac(x, y, drcp(z), c.fx, c.fy, J);
-#pragma unroll
-      for (int a = 0; a < 6; a++) {
-        c0 -= w * J[0][a] * xb[a];
-        c1 -= w * J[1][a] * xb[a];
-      }
-    }
-    const double ihl = drcp(h + lam);
-    double xl0 = c0 * ihl - h * c1 * ihl * ilam;
-    if (i > 0) xl0 += c0 * ilam;  // stride-2 spill of landmark i-1's third Dinv row
-    it.xl[0] = xl0;
-    it.xl[1] = c1 * ilam;
-  }
+  if (ok2) back_substitute(c, P, it, i, lam, ilam, xb, Bcur);
   const double xl0 = it.xl[0], xl1 = it.xl[1];
   const double sc = xl0 * (lam * xl0 + bl0) + xl1 * (lam * xl1 + bl1);
   double mh = 0;
@@ -661,35 +656,37 @@ __device__ __forceinline__ void centre_sum_wave(const FlowSolveDesc& D, int N) {
   }
 }
 
-// N edges from edge `lo` on (a slice of the solve's edges when SPLIT, which then meets the other
-// workgroups at every reduction through gx)
+constexpr int kFlowThreads = 256;  // the largest workgroup of k_flow_lm / k_flow_lm_split
+// flow_lm_body<2, true> runs the fused trial when every slice of the solve has at most this many
+// edges: they all sit in the two register items of its threads
+constexpr int kFusedSliceMax = 2 * kFlowThreads;
+
+// The LM solve over N edges from edge `lo` on, IR register items per thread (a slice of the
+// solve's edges when SPLIT, which then meets the other workgroups at every reduction through gx).
+// The trial pass is a property of the instantiation (the dispatch in k_flow_lm / k_flow_lm_split
+// guarantees IR == 1 => N <= nt):
+//   <1, *>      fused pass, 63 sums in registers; no item outside the registers
+//   <2, false>  two-pass trial, sums through the tile, items from 2 nt on in the global arrays
+//   <2, true>   fused pass through the tile when every slice has at most kFusedSliceMax edges
+//               (the same answer in every workgroup), the two-pass trial otherwise
 template <int IR, bool SPLIT>
 __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int lo, int nt,
-                                             LMSmem& sm, int max_cand, GridX& gx,
-                                             bool spec_ok = false) {
+                                             LMSmem& sm, int max_cand, GridX& gx) {
+  static_assert(IR == 1 || IR == 2, "one or two register items per thread");
   const int tid = threadIdx.x, nw = nt >> 6;
 #ifdef MMT_LM_PROFILE
   long long prof_t = 0;
   if (tid == 0)
     for (int k = 0; k < 12; k++) sm.prof[k] = 0;
 #endif
-  double* G = D.scratch;  // items beyond IR * blockDim
+  double* G = D.scratch;  // items beyond IR * blockDim (IR == 2 only)
   const int cap = D.cap;
-  // split solve with every workgroup's edges in registers (at most 2 x 256 per slice, the same
-  // answer in every workgroup): a trial is one fused pass (errors + the linearisation at the trial
-  // state) and one exchange, instead of a light pass, an exchange, and for accepted trials a
-  // second pass and exchange.  The ego solve accepts nearly every trial (22 of 24), so the
-  // speculative linearisation is almost never wasted.
-  // The one-workgroup solves (D3) take the same fused pass when they have one edge per thread
-  // (spec_ok: MMT_LM_SPEC1, default on).
-  const bool spec = spec_ok && (SPLIT ? (gx.ntot + gx.G - 1) / gx.G <= 2 * 256 : IR == 1 && N <= nt);
-  // the one-workgroup solves (D3) reduce the accepted trial's 63 sums in registers
-  // (the one-edge path: with two register edges the kernel would spill); max_cand bit 8 turns it
-  // on (MMT_LM_REGSUM, A/B knob)
-  const bool kRegSums = !SPLIT && IR == 1 && (max_cand & 256);
-  const bool kSpecRegSums = IR == 1 && (max_cand & 256);  // the fused pass's sums in registers
-  max_cand &= 255;
-  const int rs_idx = (kRegSums || kSpecRegSums) ? wave_rs_index() : 0;
+  // The fused trial is one pass (errors + the linearisation at the trial state) and one
+  // reduction, instead of a light pass and, for accepted trials, a second pass, each with its
+  // reduction (and exchange, when SPLIT).  The ego solve accepts nearly every trial (22 of 24),
+  // so the speculative linearisation is almost never wasted.
+  const bool fused = IR == 1 || (SPLIT && (gx.ntot + gx.G - 1) / gx.G <= kFusedSliceMax);
+  const int rs_idx = IR == 1 ? wave_rs_index() : 0;  // block_sum_regs64's lane permutation
   Cam c;
   c.fx = D.fx;
   c.fy = D.fy;
@@ -734,16 +731,16 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
   };
   LMItem R[IR];
   const int n_reg = IR * nt;
-  // one edge per thread: keep w J of the current linearisation in registers, so the
-  // back-substitution needs no projection
-  constexpr bool kCacheB = true;  // register item 0 of every thread
+  // w J of register item 0 at the current linearisation, so its back-substitution needs no
+  // projection
   double RB[12];
   // The LM bookkeeping below is computed redundantly by every thread from the block sums in LDS
   // (identical inputs, identical results), so only the 6x6 solve needs a lane-0 section.
   DSE3 P = dse3_from_float(D.init_dev ? D.init_dev : D.init);
   const double hin = kInfo + c.pinfo;  // h of every edge when none is Huber-active
-  // the sums of the current system (vc): sum k in lane k of every wave
-  // ---- initial linearisation (computeActiveErrors + buildSystem at the initial estimate)
+  // ---- initial linearisation (all; global items <2, *>): computeActiveErrors + buildSystem at
+  // the initial estimate, through the tile.  vc: the sums of the current system, sum k in lane k
+  // of every wave
   double* row = tile_row(sm.tile);  // this thread's row of the reduction tile
   // every thread with an edge has one in register slot 0 (N > nt implies all do), so slot 0
   // stores the row and everything after accumulates; threads without edges zero it
@@ -756,19 +753,20 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
         init_item(lo + i, R[k]);
         if (k == 0)
           linearise<true>(c, P, R[k], R[k].f[0], R[k].f[1], row, 0.0, R[k].e[0], R[k].e[1],
-                          R[k].w, R[k].bl[0], R[k].bl[1], mh, kCacheB ? RB : nullptr);
+                          R[k].w, R[k].bl[0], R[k].bl[1], mh, RB);
         else
           linearise<false>(c, P, R[k], R[k].f[0], R[k].f[1], row, 0.0, R[k].e[0], R[k].e[1],
                            R[k].w, R[k].bl[0], R[k].bl[1], mh);
       }
     }
-    for (int i = n_reg + tid; i < N; i += nt) {
-      LMItem it;
-      init_item(lo + i, it);
-      linearise<false>(c, P, it, it.f[0], it.f[1], row, 0.0, it.e[0], it.e[1], it.w, it.bl[0],
-                       it.bl[1], mh);
-      item_store(G, cap, lo + i, it);
-    }
+    if constexpr (IR == 2)
+      for (int i = n_reg + tid; i < N; i += nt) {
+        LMItem it;
+        init_item(lo + i, it);
+        linearise<false>(c, P, it, it.f[0], it.f[1], row, 0.0, it.e[0], it.e[1], it.w, it.bl[0],
+                         it.bl[1], mh);
+        item_store(G, cap, lo + i, it);
+      }
     if (tid >= N)
       for (int q = 0; q < kSums; q++) row[q] = 0;
 #pragma unroll
@@ -807,15 +805,12 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
       if (tid == 0) prof_t = clock64();
 #endif
       const double ilam = drcp(lam);
-      // ---- Schur complement over the flow vertices.  Edge i contributes
+      // ---- Schur sums (all, when some edge is Huber-active; global items <2, *>).  Edge i
+      // contributes
       //   d00 B0 B0^T + d01 B0 B1^T + d11 B1 B1^T,  d00 = 1/(h_i + lam), d11 = 1/lam, d01 = d00 - d11
       // (h_i = w_i + prior).  With no Huber-active edge every w_i is the same, so the sum is
       // d00 SA + d11 SB with lam-independent sums the linearisation already reduced: no pass.
-#ifdef MMT_LM_NO_CLOSED
-      const bool clean = false;
-#else
       const bool clean = lane_value(vc, 29) == 0;
-#endif
       double s27 = 0;  // SPLIT: the solve's Schur sums, sum k in lane k
       if (!clean) {
         double v[27];
@@ -824,23 +819,24 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
 #pragma unroll
         for (int k = 0; k < IR; k++)
           if (tid + k * nt < N) schur_terms(c, P, R[k], lam, ilam, v);
-        for (int i = n_reg + tid; i < N; i += nt) {
-          LMItem it;
-          item_load(G, cap, lo + i, it);
-          schur_terms(c, P, it, lam, ilam, v);
-        }
+        if constexpr (IR == 2)
+          for (int i = n_reg + tid; i < N; i += nt) {
+            LMItem it;
+            item_load(G, cap, lo + i, it);
+            schur_terms(c, P, it, lam, ilam, v);
+          }
         MMT_LMPROF(4);
         block_sum_t<27>(v, sm.tile, sm.red, sm.S27, nw);
         if (SPLIT) s27 = gx_sum(gx, (tid & 63) < 27 ? sm.S27[tid & 63] : 0.0, 27);
       }
       MMT_LMPROF(0);
-      // the 6x6 solve, computed redundantly by every wave from the sums (no lane-0 section, no
-      // barrier).  A rejected trial changes only lambda (lam *= ni, ni *= 2), so on the
-      // closed-form path the four 16-lane groups of a wave solve for the next four lambdas of the
-      // rejection chain at once (the same instructions, a different lambda per lane): a trial
-      // after a rejection takes its increment and pose from the wave's candidate table instead of
-      // paying the solve's dependency chain again.  Each candidate is computed exactly as the
-      // sequential solve for its lambda would be.
+      // ---- candidate solves (all): the 6x6 solve, computed redundantly by every wave from the
+      // sums (no lane-0 section, no barrier).  A rejected trial changes only lambda (lam *= ni,
+      // ni *= 2), so on the closed-form path the four 16-lane groups of a wave solve for the next
+      // four lambdas of the rejection chain at once (the same instructions, a different lambda per
+      // lane): a trial after a rejection takes its increment and pose from the wave's candidate
+      // table instead of paying the solve's dependency chain again.  Each candidate is computed
+      // exactly as the sequential solve for its lambda would be.
       if (!(clean && kc < ncand)) {
         double lg = lam, ilg = ilam;
         if (clean) {
@@ -931,56 +927,57 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
       }
       MMT_LMPROF(1);
       double lastTrialChi, scale;
-      // split solve, every edge in registers: one fused pass and one exchange per trial (below)
-      double vn = 0;                        // the trial's sums; the next system if accepted
-      double pw[IR], pb0[IR], pb1[IR];      // pending w, bl of the register items
-      double RBn[12];                       // pending w J of register item 0
-      if (IR == 1 && spec && kSpecRegSums) {
-        // the fused pass with its sums in registers (as D3's pass 2)
-        double vals[64];
-        if (tid < N)
-          spec_terms<true>(c, P, PN, R[0], lo + tid, ok2, lam, ilam, xb, vals, pw[0], pb0[0],
-                           pb1[0], kCacheB ? RB : nullptr, RBn);
-        else
+      double vn = 0;                    // the fused trial's sums; the next system if accepted
+      double pw[IR], pb0[IR], pb1[IR];  // ... and its pending w, bl of the register items
+      double RBn[12];                   // ... and pending w J of register item 0
+      if (fused) {
+        if constexpr (IR == 1) {
+          // ---- trial pass, fused, sums in registers (<1, *>): a register reduce-scatter
+          // (block_sum_regs64) instead of the tile
+          double vals[64];
+          if (tid < N)
+            fused_terms<true>(c, P, PN, R[0], lo + tid, ok2, lam, ilam, xb, vals, pw[0], pb0[0],
+                              pb1[0], RB, RBn);
+          else
 #pragma unroll
-          for (int q = 0; q < 64; q++) vals[q] = 0;
-        vals[63] = 0;
-        MMT_LMPROF(5);
-        vn = block_sum_regs64(vals, sm.part[pb], nw, rs_idx);
-        pb ^= 1;
-        if (SPLIT) vn = gx_sum(gx, vn, kSums);
-        lastTrialChi = lane_value(vn, 0);
-        scale = lane_value(vn, 1);
-      } else if (spec) {
+            for (int q = 0; q < 64; q++) vals[q] = 0;
+          vals[63] = 0;
+          MMT_LMPROF(5);
+          vn = block_sum_regs64(vals, sm.part[pb], nw, rs_idx);
+        } else {
+          // ---- trial pass, fused, sums through the tile (<2, true>, slices <= kFusedSliceMax)
 #pragma unroll
-        for (int k = 0; k < IR; k++) {
-          const int i = tid + k * nt;
-          if (i < N) {
-            if (k == 0)
-              spec_terms<true>(c, P, PN, R[k], lo + i, ok2, lam, ilam, xb, row, pw[k], pb0[k],
-                               pb1[k], kCacheB ? RB : nullptr, RBn);
-            else
-              spec_terms<false>(c, P, PN, R[k], lo + i, ok2, lam, ilam, xb, row, pw[k], pb0[k],
-                                pb1[k], nullptr, nullptr);
+          for (int k = 0; k < IR; k++) {
+            const int i = tid + k * nt;
+            if (i < N) {
+              if (k == 0)
+                fused_terms<true>(c, P, PN, R[k], lo + i, ok2, lam, ilam, xb, row, pw[k], pb0[k],
+                                  pb1[k], RB, RBn);
+              else
+                fused_terms<false>(c, P, PN, R[k], lo + i, ok2, lam, ilam, xb, row, pw[k], pb0[k],
+                                   pb1[k], nullptr, nullptr);
+            }
           }
+          if (tid >= N)
+            for (int q = 0; q < kSums; q++) row[q] = 0;
+          MMT_LMPROF(5);
+          vn = block_sum_tile_lanes<kSums>(sm.tile, sm.part[pb], nw);
         }
-        if (tid >= N)
-          for (int q = 0; q < kSums; q++) row[q] = 0;
-        MMT_LMPROF(5);
-        vn = block_sum_tile_lanes<kSums>(sm.tile, sm.part[pb], nw);
         pb ^= 1;
         if (SPLIT) vn = gx_sum(gx, vn, kSums);
         lastTrialChi = lane_value(vn, 0);
         scale = lane_value(vn, 1);
-      } else {
-      // ---- pass 1: flow back-substitution and the trial's errors (chi2 and scale sums only)
+      } else if constexpr (IR == 2) {
+        // ---- trial pass 1 (<2, false>; <2, true>, slices > kFusedSliceMax): flow
+        // back-substitution and the trial's errors (chi2 and scale sums only), so a rejected
+        // trial costs this light pass and a DPP reduction of two sums
         double s_chi = 0, s_sc = 0;
 #pragma unroll
         for (int k = 0; k < IR; k++) {
           const int i = tid + k * nt;
           if (i < N)
             trial_terms(c, P, PN, R[k], lo + i, ok2, lam, ilam, xb, s_chi, s_sc,
-                        (kCacheB && k == 0) ? RB : nullptr);
+                        k == 0 ? RB : nullptr);
         }
         {  // global items: the next item's loads are in flight while this one computes
           int i = n_reg + tid;
@@ -1004,10 +1001,10 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
         }
       }
       MMT_LMPROF(2);
-      // ---- g2o LM step acceptance and termination (every thread, same values).  The policy of
-      // mmt_lmstep.h, written out: calling LMStep here changed the register allocation of this
-      // kernel (it sits at the 256-VGPR ceiling) and cost 0.5-0.9 % of the bench (DESIGN.md
-      // section 4).  Keep the two in step.
+      // ---- decision (all): g2o LM step acceptance and termination (every thread, same values).
+      // The policy of mmt_lmstep.h, written out: calling LMStep here changed the register
+      // allocation of this kernel (it sits at the 256-VGPR ceiling) and cost 0.5-0.9 % of the
+      // bench.  Keep the two in step.
       const double tempChi = ok2 ? lastTrialChi : DBL_MAX;
 #pragma unroll
       for (int a = 0; a < 6; a++) scale += xb[a] * (lam * xb[a] + lane_value(vc, 23 + a));
@@ -1044,85 +1041,59 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
         iters = iter + 1;
         bad = !ok;
       }
-      if (accept && spec) {
-        // the fused pass already linearised at the accepted state: take the flow step and the
-        // pending state, and the trial's sums become the current system
+      if (accept) {
+        if (fused) {
+          // ---- adopt, fused (<1, *>; <2, true>, slices <= kFusedSliceMax): the pass already
+          // linearised at the accepted state; take the flow step and the pending state, and the
+          // trial's sums become the current system
 #pragma unroll
-        for (int k = 0; k < IR; k++)
-          if (tid + k * nt < N) {
-            R[k].f[0] += R[k].xl[0];
-            R[k].f[1] += R[k].xl[1];
-            R[k].w = pw[k];
-            R[k].bl[0] = pb0[k];
-            R[k].bl[1] = pb1[k];
-          }
-        if (kCacheB && tid < N)
+          for (int k = 0; k < IR; k++)
+            if (tid + k * nt < N) {
+              R[k].f[0] += R[k].xl[0];
+              R[k].f[1] += R[k].xl[1];
+              R[k].w = pw[k];
+              R[k].bl[0] = pb0[k];
+              R[k].bl[1] = pb1[k];
+            }
+          if (tid < N)
 #pragma unroll
-          for (int a = 0; a < 12; a++) RB[a] = RBn[a];
-        vc = vn;
-      } else if (IR == 1 && !SPLIT && accept && kRegSums) {
-        // ---- pass 2 with its sums in registers: the thread's edges accumulate into vals, and a
-        // register reduce-scatter (block_sum_regs64) replaces the LDS tile
-        double vals[64];
+            for (int a = 0; a < 12; a++) RB[a] = RBn[a];
+          vc = vn;
+        } else if constexpr (IR == 2) {
+          // ---- adopt, trial pass 2 (<2, false>; <2, true>, slices > kFusedSliceMax): take the
+          // flow step and linearise at the accepted state (the system of the next trial)
 #pragma unroll
-        for (int k = 0; k < IR; k++)
-          if (tid + k * nt < N) {
-            if (k == 0)
-              accept_terms<true>(c, P, R[k], vals, kCacheB ? RB : nullptr);
-            else
-              accept_terms<false>(c, P, R[k], vals);
+          for (int k = 0; k < IR; k++)
+            if (tid + k * nt < N) {
+              if (k == 0)
+                accept_terms<true>(c, P, R[k], row, RB);
+              else
+                accept_terms<false>(c, P, R[k], row);
+            }
+          {
+            int i = n_reg + tid;
+            LMItem it, nx;
+            if (i < N) item_load(G, cap, lo + i, it);
+            for (; i < N; i += nt) {
+              if (i + nt < N) item_load(G, cap, lo + i + nt, nx);
+              accept_terms<false>(c, P, it, row);
+              item_store_accept(G, cap, lo + i, it);
+              it = nx;
+            }
           }
-        {
-          int i = n_reg + tid;
-          LMItem it, nx;
-          if (i < N) item_load(G, cap, lo + i, it);
-          for (; i < N; i += nt) {
-            if (i + nt < N) item_load(G, cap, lo + i + nt, nx);
-            accept_terms<false>(c, P, it, vals);
-            item_store_accept(G, cap, lo + i, it);
-            it = nx;
-          }
-        }
-        if (tid >= N)
-#pragma unroll
-          for (int q = 0; q < 64; q++) vals[q] = 0;
-        vals[63] = 0;
-        vc = block_sum_regs64(vals, sm.part[pb], nw, rs_idx);
-        pb ^= 1;
-      } else if (accept) {
-        // ---- pass 2: take the flow step and linearise at the accepted state (the system of the
-        // next trial); rejected trials skip it, so they cost the errors and two sums only
-#pragma unroll
-        for (int k = 0; k < IR; k++)
-          if (tid + k * nt < N) {
-            if (k == 0)
-              accept_terms<true>(c, P, R[k], row, kCacheB ? RB : nullptr);
-            else
-              accept_terms<false>(c, P, R[k], row);
-          }
-        {
-          int i = n_reg + tid;
-          LMItem it, nx;
-          if (i < N) item_load(G, cap, lo + i, it);
-          for (; i < N; i += nt) {
-            if (i + nt < N) item_load(G, cap, lo + i + nt, nx);
-            accept_terms<false>(c, P, it, row);
-            item_store_accept(G, cap, lo + i, it);
-            it = nx;
-          }
-        }
-        if (tid >= N)
-          for (int q = 0; q < kSums; q++) row[q] = 0;
+          if (tid >= N)
+            for (int q = 0; q < kSums; q++) row[q] = 0;
 #ifdef MMT_LM_PROFILE
-        if (tid == 0) {  // pass 2's edge work, apart from its reduction (decide keeps the rest)
-          const long long now = clock64();
-          sm.prof[10] += now - prof_t;
-          prof_t = now;
-        }
+          if (tid == 0) {  // pass 2's edge work, apart from its reduction (decide keeps the rest)
+            const long long now = clock64();
+            sm.prof[10] += now - prof_t;
+            prof_t = now;
+          }
 #endif
-        vc = block_sum_tile_lanes<kSums>(sm.tile, sm.part[pb], nw);
-        pb ^= 1;
-        if (SPLIT) vc = gx_sum(gx, vc, kSums);
+          vc = block_sum_tile_lanes<kSums>(sm.tile, sm.part[pb], nw);
+          pb ^= 1;
+          if (SPLIT) vc = gx_sum(gx, vc, kSums);
+        }
       }
       MMT_LMPROF(3);
 #ifdef MMT_LM_PROFILE
@@ -1135,7 +1106,8 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
     }
     if (bad) break;
   }
-  // outputs: pose, iterations, inliers from the last computed edge errors (Optimizer.cc:536-566)
+  // ---- outputs (all; global items <2, *>): pose, iterations, inliers from the last computed
+  // edge errors (Optimizer.cc:536-566)
   double v[1] = {0};
   auto outlier = [&](const LMItem& it) {
     const float chi2 = (float)(kInfo * (it.e[0] * it.e[0] + it.e[1] * it.e[1]));
@@ -1144,11 +1116,12 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
 #pragma unroll
   for (int k = 0; k < IR; k++)
     if (tid + k * nt < N) v[0] += outlier(R[k]);
-  for (int i = n_reg + tid; i < N; i += nt) {
-    LMItem it;
-    item_load(G, cap, lo + i, it);
-    v[0] += outlier(it);
-  }
+  if constexpr (IR == 2)
+    for (int i = n_reg + tid; i < N; i += nt) {
+      LMItem it;
+      item_load(G, cap, lo + i, it);
+      v[0] += outlier(it);
+    }
   block_sum<1>(v, sm.red, sm.S27, nw);
   int n_out = N - (int)sm.S27[0], status = 0;
   if (SPLIT) {  // the solve's outliers, and whether any workgroup gave up waiting
@@ -1177,11 +1150,10 @@ __device__ __forceinline__ void flow_lm_body(const FlowSolveDesc& D, int N, int 
 
 // One workgroup per solve; each workgroup picks the register-item count its own edge count needs,
 // so a small object solved in the same launch as a large one runs the short code path.
-template <int MAXIR>
 // max_cand (1..4): lambda candidates a clean system's solve provides (1: every trial solves for
 // its own lambda, the sequential order; a test knob, candidates are bit-identical to it)
-__global__ __launch_bounds__(256) void k_flow_lm(const FlowSolveDesc* __restrict__ descs,
-                                                 int max_cand) {
+__global__ __launch_bounds__(kFlowThreads) void k_flow_lm(const FlowSolveDesc* __restrict__ descs,
+                                                          int max_cand) {
   __shared__ LMSmem sm;
   const FlowSolveDesc& D = descs[blockIdx.x];
   const int N = D.d_n ? min(*D.d_n, D.cap) : min(D.n, D.cap);
@@ -1203,18 +1175,18 @@ __global__ __launch_bounds__(256) void k_flow_lm(const FlowSolveDesc* __restrict
   const int nt = min((int)blockDim.x, max(64, (N + 63) / 64 * 64));
   if ((int)threadIdx.x >= nt) return;
   GridX gx{};
-  const bool spec = (max_cand & 512) != 0;
-  if (N <= nt || MAXIR == 1)
-    flow_lm_body<1, false>(D, N, 0, nt, sm, max_cand, gx, spec);
+  // flow_lm_body<1, *> holds no item outside register slot 0: it is entered with N <= nt only
+  if (N <= nt)
+    flow_lm_body<1, false>(D, N, 0, nt, sm, max_cand, gx);
   else
-    flow_lm_body<2, false>(D, N, 0, nt, sm, max_cand, gx, spec);
+    flow_lm_body<2, false>(D, N, 0, nt, sm, max_cand, gx);
 }
 
 // One large solve (descs[0]) over gridDim.x <= kFlowSplitMax workgroups, each on a contiguous slice
 // of the edges (lo = b N / G); the LM bookkeeping runs in every workgroup on the exchanged sums.
 // The workgroups must be resident together: one per CU, at most 8 (bounded spins otherwise).
-__global__ __launch_bounds__(256) void k_flow_lm_split(const FlowSolveDesc* __restrict__ descs,
-                                                       int max_cand, int spec) {
+__global__ __launch_bounds__(kFlowThreads) void k_flow_lm_split(
+    const FlowSolveDesc* __restrict__ descs, int max_cand) {
   __shared__ LMSmem sm;
   const FlowSolveDesc& D = descs[0];
   const int N = D.d_n ? min(*D.d_n, D.cap) : min(D.n, D.cap);
@@ -1235,10 +1207,21 @@ __global__ __launch_bounds__(256) void k_flow_lm_split(const FlowSolveDesc* __re
   const int nt = min((int)blockDim.x, max(64, (Nl + 63) / 64 * 64));
   if ((int)threadIdx.x >= nt) return;
   GridX gx{D.gx, D.gx_seq, b, G, 0, N, false, D.gx_spin ? D.gx_spin : 10000000ull};
+  // As k_flow_lm: <1, true> is entered with Nl <= nt only.  Every workgroup of a solve must run
+  // the same trial (the exchanges pair up), and slices differ by at most one edge: a workgroup
+  // in <1, true> (always fused) has Nl <= kFlowThreads, so the largest slice, ceil(N / G), is at
+  // most kFlowThreads + 1 <= kFusedSliceMax and a neighbour in <2, true> runs the fused trial too.
+  static_assert(kFlowThreads + 1 <= kFusedSliceMax, "<1, true> and <2, true> must agree");
   if (Nl <= nt)
-    flow_lm_body<1, true>(D, Nl, lo, nt, sm, max_cand, gx, spec != 0);
+    flow_lm_body<1, true>(D, Nl, lo, nt, sm, max_cand, gx);
   else
-    flow_lm_body<2, true>(D, Nl, lo, nt, sm, max_cand, gx, spec != 0);
+    flow_lm_body<2, true>(D, Nl, lo, nt, sm, max_cand, gx);
+}
+
+// MMT_LM_MAX_CAND=1..4, default 4 (read per launch; tests compare 1 against 4 bit for bit)
+static int flow_max_cand() {
+  const char* e = getenv("MMT_LM_MAX_CAND");
+  return e ? std::min(4, std::max(1, atoi(e))) : 4;
 }
 
 void launch_flow_lm(const FlowSolveDesc* d_descs, int nsolves, int n_hint, hipStream_t st) {
@@ -1247,13 +1230,8 @@ void launch_flow_lm(const FlowSolveDesc* d_descs, int nsolves, int n_hint, hipSt
   // items each (more register items spill: the 6x6 solve and the sums need the room); items
   // beyond go through the global item arrays.  Each workgroup picks its own item count
   // (k_flow_lm); n_hint (the largest edge count) only sizes the block.
-  const int threads = std::min(256, std::max(64, (n_hint + 63) / 64 * 64));
-  // MMT_LM_MAX_CAND=1..4 (read per launch; tests compare 1 against the default 4 bit for bit);
-  // bit 256: the accepted trial's sums reduced in registers; bit 512: the fused trial pass
-  int max_cand = 4;
-  if (const char* e = getenv("MMT_LM_MAX_CAND")) max_cand = std::min(4, std::max(1, atoi(e)));
-  max_cand |= 256 | 512;
-  hipLaunchKernelGGL(k_flow_lm<2>, dim3(nsolves), dim3(threads), 0, st, d_descs, max_cand);
+  const int threads = std::min(kFlowThreads, std::max(64, (n_hint + 63) / 64 * 64));
+  hipLaunchKernelGGL(k_flow_lm, dim3(nsolves), dim3(threads), 0, st, d_descs, flow_max_cand());
 }
 
 int flow_split_groups(int n_hint) {
@@ -1268,12 +1246,9 @@ int flow_split_groups(int n_hint) {
 }
 
 void launch_flow_lm_split(const FlowSolveDesc* d_desc, int groups, hipStream_t st) {
-  int max_cand = 4;
-  if (const char* e = getenv("MMT_LM_MAX_CAND")) max_cand = std::min(4, std::max(1, atoi(e)));
   groups = std::max(1, std::min(groups, kFlowSplitMax));
-  const int spec = 1;  // one fused pass and one exchange per trial
-  max_cand |= 256;     // its sums reduced in registers
-  hipLaunchKernelGGL(k_flow_lm_split, dim3(groups), dim3(256), 0, st, d_desc, max_cand, spec);
+  hipLaunchKernelGGL(k_flow_lm_split, dim3(groups), dim3(kFlowThreads), 0, st, d_desc,
+                     flow_max_cand());
 }
 
 size_t flow_scratch_doubles(int cap) { return (size_t)G_COUNT * cap; }

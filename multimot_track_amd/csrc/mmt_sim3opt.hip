@@ -220,7 +220,8 @@ struct SoSmem {
 
 // Eigen::LDLT<MatrixXd> of H + lambda I with diagonal pivoting (LinearSolverDense), on one lane:
 // sm.x receives the solution when the factorisation is positive (LDLT::isPositive()), and keeps its
-// values otherwise (g2o's stale increment).  Same scheme as ldlt_solve6 (mmt_devmath.h).
+// values otherwise (g2o's stale increment).  (The 6 x 6 solves of mmt_lm.hip, ldlt6_packed, are
+// unpivoted and unrolled in registers instead.)
 __device__ __noinline__ void so_solve(SoSmem& sm, const double* Hc, double lam) {
   {
     int k = 1;

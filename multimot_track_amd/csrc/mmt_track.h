@@ -104,12 +104,14 @@ struct FlowSolveDesc {
   const float* init_dev;
 };
 
-// A large single solve split over up to kFlowSplitMax workgroups (one slice of the edges each),
-// which meet at every reduction through tagged granules (flow_lm_body).
+// A large single solve (d_desc[0]) split over up to kFlowSplitMax workgroups of 256 threads (one
+// contiguous slice of the edges each), which meet at every reduction through tagged granules
+// (mmt_lm.hip: gx_sum).  Slices of at most 512 edges (every solve of up to 4096 edges at 8
+// groups) run the fused trial, one pass and one exchange; larger slices the two-pass trial.
 constexpr int kFlowSplitMax = 8;
 constexpr int kFlowSplitGranules = 2 * kFlowSplitMax * 128;
 // workgroups launch_flow_lm_split would use for an edge count (1: no split); MMT_LM_SPLIT=0
-// disables the split, MMT_LM_SPLIT=<g> forces g workgroups
+// disables the split, MMT_LM_SPLIT=<g> forces g workgroups (read per call)
 int flow_split_groups(int n_hint);
 void launch_flow_lm_split(const FlowSolveDesc* d_desc, int groups, hipStream_t st);
 
@@ -125,6 +127,10 @@ void launch_handoff(const float2* last_corres, const int* n_last, const float2* 
                     const int* n_olast, const float* depth, const int32_t* mask, int W, int H,
                     const HandoffSet& cur, hipStream_t st);
 void launch_obj_group(const GroupArgs& a, hipStream_t st);
+// nsolves solves, one workgroup each, in one launch; n_hint (the largest edge count) sizes the
+// workgroup, 64..256 threads.  A solve with at most one edge per thread runs the fused trial in
+// registers, a larger one the two-pass trial (mmt_lm.hip's header).  Both launchers read
+// MMT_LM_MAX_CAND (1..4, default 4: lambda candidates per solve of a rejection chain) per launch.
 void launch_flow_lm(const FlowSolveDesc* d_descs, int nsolves, int n_hint, hipStream_t st);
 size_t flow_scratch_doubles(int cap);
 

@@ -25,9 +25,11 @@ def _d1(name, seed, n, out, mono):
 
 
 _CHAIN = dict(outlier_frac=0.0, motion=0.3)  # large motion, little noise: runs of clean rejections
+_CLEAN = dict(pix_noise=0.0, **_CHAIN)        # no Huber-active edge
+_G2 = {"MMT_LM_SPLIT": "2"}
 
 CASES = (
-    # ---- k_flow_lm<2>
+    # ---- k_flow_lm
     _both("flow3", 5, 3, outlier_frac=0.0) +                   # the minimum
     [_flow("flow37_huber", 6, 37, EGO, outlier_frac=0.3)] +     # one wave, Huber active: no closed form
     _both("flow64", 11, 64) + _both("flow65", 12, 65) +         # wave boundary of nt
@@ -40,6 +42,14 @@ CASES = (
     [_flow("split5_g8", 9, 5, EGO, env={"MMT_LM_SPLIT": "8"}, outlier_frac=0.0),  # empty slices
      _flow("split600_g3", 1, 600, EGO, env={"MMT_LM_SPLIT": "3"}, outlier_frac=0.1),
      _flow("split_chain900_g4", 24, 900, OBJ, env={"MMT_LM_SPLIT": "4"}, pix_noise=0.02, **_CHAIN)] +
+    # flow_lm_body<2, true> (slices above 256 edges), both sides of its run-time choice, each on a
+    # Huber-active system (Schur pass and its exchange, a rejected trial) and on a clean one
+    # (closed-form Schur sums, candidates served after rejections).  Slices of 257: the fused
+    # pass through the tile; slices of 513 (> 512): the two-pass trial, one item in the global arrays
+    [_flow("split514_g2_huber", 2, 514, OBJ, env=_G2, outlier_frac=0.1),
+     _flow("split514_g2_clean", 4, 514, OBJ, env=_G2, **_CLEAN),
+     _flow("split1026_g2_huber", 2, 1026, OBJ, env=_G2, outlier_frac=0.1),
+     _flow("split1026_g2_clean", 4, 1026, OBJ, env=_G2, **_CLEAN)] +
     # ---- D1: k_pose_opt_l<2> up to 1024 edges, <4> up to 2048, k_pose_opt beyond
     [_d1("d1_3", 8, 3, 0.0, 0.3), _d1("d1_8", 3, 8, 0.0, 0.3),  # one round (< 10 edges)
      _d1("d1_60_mono_half", 2, 60, 0.3, 0.5),

@@ -10,7 +10,11 @@ The cases are the smallest shapes at which each path can go wrong: the flow solv
 wave with Huber-active edges (no closed-form Schur sums), the wave boundary (64 / 65), one item
 per thread against two (256 / 257), the first item in the global item arrays (513), rejection
 chains served from the candidate table (also with MMT_LM_MAX_CAND=1), the split solve with empty
-slices, three groups, and a rejection chain across workgroups; D1 at 3 and 8 edges (one round),
+slices, three groups, and a rejection chain across workgroups (slices of at most 256 edges), and
+slices of two register items per thread on both sides of their run-time choice, each on a
+Huber-active and on a clean system: 2 x 257 edges (the fused trial through the tile) and 2 x 513
+(above 512 per slice: the two-pass trial with an exchange per pass, one item per slice in the
+global item arrays); D1 at 3 and 8 edges (one round),
 mixed and all-mono edges, and both sides of the 1024- and 2048-edge kernel thresholds (2049 is the
 only way into the global-scratch kernel k_pose_opt)."""
 import os

@@ -20,7 +20,7 @@ for r in csv.DictReader(open(f)):
     n = name.split("(")[0].replace("void ", "").replace("mmt::", "")
     ks.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", "?"), n))
 ks.sort()
-markers = {"ego": "k_flow_lm_split", "d3": "k_flow_lm<2>", "ransac": "k_pnp_hyp<5>"}
+markers = {"ego": "k_flow_lm_split", "d3": "k_flow_lm", "ransac": "k_pnp_hyp<5>"}
 for chain, mk in markers.items():
     starts = [s for s, e, q, n in ks if n == mk]
     if len(starts) < 20:
