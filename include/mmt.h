@@ -58,6 +58,10 @@
  *   mmt_stereo_frame    <- System::TrackStereo -> Tracking::GrabImageStereo's stereo Frame
  *                          constructor Frame.cc:79-159
  *   mmt_stereo_matches  <- Frame::ComputeStereoMatches Frame.cc:849-1038
+ *   mmt_search_by_bow_keyframes
+ *                       <- ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)
+ *                          ORBmatcher.cc:897-1030 (LoopClosing::ComputeSim3 LoopClosing.cc:254-282),
+ *                          a batch of candidates
  *   mmt_sim3solver_iterate
  *                       <- Sim3Solver::SetRansacParameters + iterate, Sim3Solver.cc:114-364
  *                          (LoopClosing::ComputeSim3 LoopClosing.cc:276-303), a batch of solvers
@@ -422,6 +426,19 @@ typedef struct mmt_bow_keyframe {
 int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const mmt_kp* cur_kps,
                       const uint8_t* cur_desc, const mmt_feature_vector* cur_fv, float nn_ratio,
                       int check_orientation, int32_t* match_out, int* nmatches);
+
+/* ORBmatcher(nn_ratio, check_orientation)::SearchByBoW(pKF1, pKF2, vpMatches12) ORBmatcher.cc:897-1030
+ * for one keyframe 1 against n_cand keyframes 2 (LoopClosing.cc:254-282), one call.
+ * match12_out[c * kf1->n + i1] = the key of candidate c whose MapPoint matches key i1 of keyframe 1
+ * (vpMatches12[i1] = pKF2->mvpMapPoints[that key]) or -1; nmatches_out[c] = the return value.
+ * Unlike C4: the distance must be < TH_LOW (strict), a key of keyframe 2 without a good MapPoint is
+ * never scanned, and the rotation is keyframe 1's angle minus keyframe 2's.  n_cand <= 64; a
+ * feature may be listed once only in either keyframe's vector, and a node of a candidate holds at
+ * most 16384 features (MMT_EINVAL otherwise).  LoopClosing uses nn_ratio 0.75 with the orientation
+ * check and discards a candidate at nmatches < 20. */
+int mmt_search_by_bow_keyframes(mmt_ctx* ctx, const mmt_bow_keyframe* kf1, int n_cand,
+                                const mmt_bow_keyframe* kf2 /* n_cand */, float nn_ratio,
+                                int check_orientation, int32_t* match12_out, int32_t* nmatches_out);
 
 /* ORBmatcher::Fuse(pKF, vpMapPoints, th)'s per-point search (ORBmatcher.cc:1200-1324): the point
  * projected with the keyframe's pose (cur->Tcw), KeyFrame::IsInImage, the scale-invariance

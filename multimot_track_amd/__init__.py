@@ -352,6 +352,9 @@ def lib():
         L.mmt_search_by_bow.argtypes = [vp, ctypes.POINTER(MmtBowKeyFrame), i32, vp, vp,
                                         ctypes.POINTER(MmtFeatureVector), ctypes.c_float, i32,
                                         vp, vp]
+        L.mmt_search_by_bow_keyframes.argtypes = [vp, ctypes.POINTER(MmtBowKeyFrame), i32,
+                                                  ctypes.POINTER(MmtBowKeyFrame), ctypes.c_float,
+                                                  i32, vp, vp]
         L.mmt_search_by_projection_keyframe.argtypes = [vp, ctypes.POINTER(MmtMatchFrame),
                                                         ctypes.POINTER(MmtKeyFramePoints), vp,
                                                         ctypes.c_float, i32, vp, vp, vp, vp]
@@ -711,6 +714,36 @@ class Context:
                                             ctypes.byref(F), nnratio, int(check_orientation),
                                             _p(match), ctypes.byref(nm)))
         return nm.value, match[:len(fk)]
+
+    def search_by_bow_keyframes(self, kf1, candidates, nnratio=0.75, check_orientation=True):
+        """ORBmatcher(nnratio, check_orientation)::SearchByBoW(KeyFrame*, KeyFrame*) of keyframe 1
+        against every candidate in one call (LoopClosing::ComputeSim3).  A keyframe is
+        (fv, kps, desc, mp_ok), fv as in search_by_bow.  Returns (nmatches[n_cand],
+        match12[n_cand, n1] = the candidate's key matched to key i1 of keyframe 1, or -1)."""
+        keep = []
+
+        def keyframe(K, kf):
+            fv, kps, desc, ok = kf
+            k = np.ascontiguousarray(kps)
+            d = np.ascontiguousarray(desc, np.uint8)
+            o = np.ascontiguousarray(ok, np.uint8)
+            keep.extend([k, d, o])
+            K.n = len(k)
+            K.kps, K.desc, K.mp_valid = k.ctypes.data, d.ctypes.data, o.ctypes.data
+            K.fv = _feature_vector(fv, keep)
+
+        K1 = MmtBowKeyFrame()
+        keyframe(K1, kf1)
+        nc = len(candidates)
+        K2 = (MmtBowKeyFrame * max(nc, 1))()
+        for c, kf in enumerate(candidates):
+            keyframe(K2[c], kf)
+        match12 = np.zeros((nc, K1.n), np.int32)
+        nm = np.zeros(max(nc, 1), np.int32)
+        self._check(lib().mmt_search_by_bow_keyframes(self._h, ctypes.byref(K1), nc, K2, nnratio,
+                                                      int(check_orientation), _p(match12),
+                                                      _p(nm)))
+        return nm[:nc], match12
 
     def search_local_points(self, kps, desc, depth, tcw, Xw, normal, min_dist, max_dist, pdesc,
                             skip, th, taken=None):

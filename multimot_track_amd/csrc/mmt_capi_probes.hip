@@ -628,6 +628,97 @@ int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const
   });
 }
 
+// One keyframe of mmt_search_by_bow_keyframes appended to the staging block h: every array at a
+// 16-byte boundary, the angles alone of the keys.
+static mmt::BowKfSide stage_bow_keyframe(const mmt_bow_keyframe* k, std::vector<uint8_t>& h) {
+  auto put = [&](const void* src, size_t bytes) {
+    const size_t off = (h.size() + 15) & ~(size_t)15;
+    if (off + bytes > UINT32_MAX) throw ArgError("the keyframes exceed the staging block (4 GiB)");
+    h.resize(off + bytes);
+    if (bytes > 0) memcpy(h.data() + off, src, bytes);
+    return (uint32_t)off;
+  };
+  mmt::BowKfSide s;
+  s.n = k->n;
+  s.n_nodes = k->fv.n_nodes;
+  std::vector<float> angle((size_t)k->n);
+  for (int i = 0; i < k->n; i++) angle[i] = k->kps[i].angle;
+  s.angle = put(angle.data(), 4 * (size_t)k->n);
+  s.desc = put(k->desc, 32 * (size_t)k->n);
+  s.ok = put(k->mp_valid, (size_t)k->n);
+  const int nn = k->fv.n_nodes;
+  s.node = put(k->fv.node_id, 4 * (size_t)nn);
+  s.start = put(k->fv.node_start, nn > 0 ? 4 * ((size_t)nn + 1) : 0);
+  s.feat = put(k->fv.feat, nn > 0 ? 4 * (size_t)k->fv.node_start[nn] : 0);
+  return s;
+}
+
+static void check_bow_keyframe(const mmt_bow_keyframe* k, int max_node) {
+  if (k->n < 0) throw ArgError("negative key count");
+  if (k->n > 0 && (!k->kps || !k->desc || !k->mp_valid)) throw ArgError("null keyframe arrays");
+  std::vector<uint8_t> once((size_t)std::max(k->n, 1), 0);
+  check_feature_vector(&k->fv, k->n, &once, max_node);
+}
+
+int mmt_search_by_bow_keyframes(mmt_ctx* ctx, const mmt_bow_keyframe* kf1, int n_cand,
+                                const mmt_bow_keyframe* kf2, float nn_ratio,
+                                int check_orientation, int32_t* match12_out,
+                                int32_t* nmatches_out) {
+  if (!ctx || !kf1 || n_cand < 0 || (n_cand > 0 && (!kf2 || !nmatches_out))) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (n_cand > 64) throw ArgError("mmt_search_by_bow_keyframes: more than 64 candidates");
+    // keyframe 1: a feature listed twice would have two nodes write one match12 slot
+    check_bow_keyframe(kf1, INT32_MAX);
+    for (int c = 0; c < n_cand; c++) check_bow_keyframe(&kf2[c], mmt::kMaxMatchKeys);
+    if (n_cand == 0) return;
+    const int n1 = kf1->n;
+    if (n1 > 0 && !match12_out) throw ArgError("null match12_out");
+    const size_t rows = (size_t)n_cand * (size_t)n1;
+    if (n1 == 0 || kf1->fv.n_nodes == 0) {  // nothing is replayed
+      for (size_t i = 0; i < rows; i++) match12_out[i] = -1;
+      for (int c = 0; c < n_cand; c++) nmatches_out[c] = 0;
+      return;
+    }
+    // the staging block: candidate table, keyframe 1, the candidates, the wide triples
+    std::vector<uint8_t> h(sizeof(mmt::BowKfSide) * (size_t)n_cand);
+    mmt::BowKfArgs a;
+    a.kf1 = stage_bow_keyframe(kf1, h);
+    std::vector<int4> wide;
+    for (int c = 0; c < n_cand; c++) {
+      const mmt::BowKfSide s = stage_bow_keyframe(&kf2[c], h);
+      memcpy(h.data() + sizeof(s) * (size_t)c, &s, sizeof(s));
+      if (s.n_nodes > 0)
+        mmt::bow_kf_wide_triples(c, kf1->fv.node_id, kf1->fv.n_nodes, kf2[c].fv.node_id,
+                                 kf2[c].fv.node_start, s.n_nodes, wide);
+    }
+    const size_t wide_off = (h.size() + 15) & ~(size_t)15;
+    h.resize(wide_off + sizeof(int4) * wide.size());
+    if (!wide.empty()) memcpy(h.data() + wide_off, wide.data(), sizeof(int4) * wide.size());
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    DevBuf<uint8_t> blk(h.size());
+    DevBuf<int> out(rows + (size_t)n_cand), scratch(31 * (size_t)n_cand);
+    blk.up(h, s);
+    a.blk = blk.p;
+    a.cand = reinterpret_cast<const mmt::BowKfSide*>(blk.p);
+    a.wide = reinterpret_cast<const int4*>(blk.p + wide_off);
+    a.n_cand = n_cand;
+    a.n_wide = (int)wide.size();
+    a.ratio = nn_ratio;
+    a.check_orientation = check_orientation;
+    a.match12 = out.p;
+    a.nmatches = out.p + rows;
+    a.hist = scratch.p;
+    a.counters = scratch.p + 30 * (size_t)n_cand;
+    mmt::launch_search_by_bow_keyframes(a, s);
+    std::vector<int> r(rows + (size_t)n_cand);
+    out.down(r.data(), r.size(), s);
+    MMT_HIP(hipStreamSynchronize(s));
+    memcpy(match12_out, r.data(), 4 * rows);
+    memcpy(nmatches_out, r.data() + rows, 4 * (size_t)n_cand);
+  });
+}
+
 int mmt_search_by_projection_keyframe(mmt_ctx* ctx, const mmt_match_frame* cur,
                                       const mmt_keyframe_points* pts, const uint8_t* skip,
                                       float th, int orb_dist, const uint8_t* bound_in,

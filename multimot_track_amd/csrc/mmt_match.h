@@ -144,6 +144,39 @@ void launch_search_by_bow(const BowFeatVec& kf, const mmt_kp* kf_keys, const uin
                           int* match, int* hist, int* counters, const int2* wide, int n_wide,
                           hipStream_t st);
 
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&) ORBmatcher.cc:897-1030 for one
+// keyframe 1 against n_cand keyframes 2 (LoopClosing::ComputeSim3).  Every array of every keyframe
+// lies in one staging block; a keyframe is the byte offsets of its arrays from the block's start.
+struct BowKfSide {
+  int n, n_nodes;
+  uint32_t angle;  // n floats: mvKeysUn[i].angle
+  uint32_t desc;   // n x 32
+  uint32_t ok;     // n bytes: mvpMapPoints[i] holds a MapPoint that is not bad
+  uint32_t node;   // n_nodes ids, ascending
+  uint32_t start;  // n_nodes + 1
+  uint32_t feat;   // start[n_nodes] features, a feature in one node only
+};
+struct BowKfArgs {
+  const uint8_t* blk;     // the staging block
+  BowKfSide kf1;
+  const BowKfSide* cand;  // n_cand, inside the block
+  const int4* wide;       // bow_kf_wide_triples' list, inside the block
+  int n_cand, n_wide;
+  float ratio;
+  int check_orientation;
+  int* match12;   // n_cand rows of kf1.n: key of the candidate, or -1
+  int* nmatches;  // n_cand
+  int* hist;      // n_cand x 30, scratch
+  int* counters;  // n_cand, scratch
+};
+// The (candidate, node index of keyframe 1, node index of the candidate) triples of the common
+// nodes whose candidate node is wide (more than kBowMaxNodeFeatures features); w is unused.
+void bow_kf_wide_triples(int cand, const uint32_t* node1, int n_nodes1, const uint32_t* node2,
+                         const int* start2, int n_nodes2, std::vector<int4>& out);
+// Clears match12 / hist / counters, then the narrow kernel (one wave per node of keyframe 1 and
+// candidate), the wide kernel (one workgroup per triple) and the per-candidate rotation filter.
+void launch_search_by_bow_keyframes(const BowKfArgs& a, hipStream_t st);
+
 // The edge list of Optimizer::PoseOptimization (Optimizer.cc:3160-3230) built on the device from a
 // matcher's output, in key order: key i is an edge when match[i] >= 0 (position src_X[match[i]],
 // or pool[ids[match[i]]].Xw with a pool) or, without a new match, when has_base[i] (base_X[i]);

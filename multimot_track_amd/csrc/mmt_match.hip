@@ -1312,6 +1312,291 @@ void launch_search_by_bow(const BowFeatVec& kf, const mmt_kp* kf_keys, const uin
   MMT_HIP(hipGetLastError());
 }
 
+// ------------------------------------------------------------------------------ loop candidates
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, ...) ORBmatcher.cc:897-1030, keyframe 1 against a
+// batch of candidates (LoopClosing::ComputeSim3).  The replay is C4's with keyframe 1 as the
+// replayed side and the candidate as the scanned side; what differs from C4:
+//   - bestDist1 < TH_LOW, strict (:979);
+//   - a candidate key without a good MapPoint is never scanned (:954-958): it starts out "taken";
+//   - the output is indexed by keyframe 1's key and holds the candidate's key (:983), the
+//     histogram holds keyframe 1's keys and rotates angle1 - angle2 (:988);
+//   - every candidate has its own matched flags, histogram, counter and match12 row.
+// C4's kernels are on the per-frame path and stay as they are; these stand beside them.
+struct BowKfView {
+  const float* angle;
+  const uint8_t* desc;
+  const uint8_t* ok;
+  const uint32_t* node;
+  const int* start;
+  const int* feat;
+};
+__device__ __forceinline__ BowKfView bow_kf_view(const uint8_t* blk, const BowKfSide& s) {
+  BowKfView v;
+  v.angle = reinterpret_cast<const float*>(blk + s.angle);
+  v.desc = blk + s.desc;
+  v.ok = blk + s.ok;
+  v.node = reinterpret_cast<const uint32_t*>(blk + s.node);
+  v.start = reinterpret_cast<const int*>(blk + s.start);
+  v.feat = reinterpret_cast<const int*>(blk + s.feat);
+  return v;
+}
+
+// rotHist[bin].push_back(idx1) as a count; angles outside [0, 360) (the reference asserts the bin)
+// count nowhere
+__device__ __forceinline__ void bow_kf_hist_add(int* hist, int cand, float a1, float a2) {
+  const int bin = rot_bin(a1, a2);
+  if ((unsigned)bin < (unsigned)HISTO_LENGTH) atomicAdd(&hist[HISTO_LENGTH * cand + bin], 1);
+}
+
+// one wave per (node of keyframe 1, candidate); lane = position in the candidate's node, 64 c apart
+__global__ __launch_bounds__(256) void k_bow_kf_nodes(BowKfArgs a) {
+  const int k = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (k >= a.kf1.n_nodes) return;  // wave-uniform
+  const int lane = threadIdx.x & 63;
+  const int cand = blockIdx.y;
+  const BowKfSide s2 = a.cand[cand];
+  const BowKfView v1 = bow_kf_view(a.blk, a.kf1), v2 = bow_kf_view(a.blk, s2);
+  const uint32_t id = v1.node[k];
+  int lo = 0, hi = s2.n_nodes;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (v2.node[mid] < id)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  if (lo >= s2.n_nodes || v2.node[lo] != id) return;
+  const int fb = v2.start[lo], fn = v2.start[lo + 1] - fb;
+  if (fn > kBowMaxNodeFeatures) return;  // wave-uniform: k_bow_kf_nodes_wide's node
+  const int nch = (fn + 63) >> 6;  // <= 32
+  // bit c: position lane + 64 c is matched, past the node's end or without a good MapPoint
+  uint32_t taken = 0;
+  for (int c = 0; c < nch; c++) {
+    const int p = lane + 64 * c;
+    if (p >= fn || !v2.ok[v2.feat[fb + p]]) taken |= 1u << c;
+  }
+  int* row = a.match12 + (size_t)cand * (size_t)a.kf1.n;
+  int nm = 0;
+  for (int q = v1.start[k]; q < v1.start[k + 1]; q++) {
+    const int i1 = v1.feat[q];
+    if (!v1.ok[i1]) continue;  // pMP1 == NULL or isBad()
+    uint32_t dk[8];
+    load_desc8(v1.desc + 32 * (size_t)i1, dk);
+    uint32_t k1 = kNoCand;  // lane-local smallest (dist << 16 | position)
+    int d2 = 256;           // lane-local second-smallest distance
+    for (int c = 0; c < nch; c++) {
+      if ((taken >> c) & 1u) continue;
+      const int p = lane + 64 * c;
+      uint32_t df[8];
+      load_desc8(v2.desc + 32 * (size_t)v2.feat[fb + p], df);
+      int dist = 0;
+#pragma unroll
+      for (int w = 0; w < 8; w++) dist += __popc(dk[w] ^ df[w]);
+      const uint32_t key = ((uint32_t)dist << 16) | (uint32_t)p;
+      if (key < k1) {
+        if (k1 != kNoCand) d2 = min(d2, (int)(k1 >> 16));
+        k1 = key;
+      } else {
+        d2 = min(d2, dist);
+      }
+    }
+    const uint32_t m1 = wave_min_u32(k1);
+    if (m1 == kNoCand) continue;  // bestDist1 = 256
+    const int c2 = k1 == m1 ? d2 : (k1 != kNoCand ? (int)(k1 >> 16) : 256);
+    const int best2 = (int)wave_min_u32((uint32_t)c2);
+    const int best1 = (int)(m1 >> 16);
+    if (best1 >= TH_LOW || !((float)best1 < a.ratio * (float)best2)) continue;
+    const int p = (int)(m1 & 0xFFFFu);
+    if (lane == (p & 63)) {
+      taken |= 1u << (p >> 6);
+      const int i2 = v2.feat[fb + p];
+      row[i1] = i2;
+      if (a.check_orientation) bow_kf_hist_add(a.hist, cand, v1.angle[i1], v2.angle[i2]);
+    }
+    nm++;
+  }
+  if (lane == 0 && nm) atomicAdd(&a.counters[cand], nm);
+}
+
+// A candidate node of 2049..kMaxMatchKeys features: one 512-thread workgroup per (candidate, node
+// of keyframe 1, node of the candidate) triple, k_bow_nodes_wide's replay (thread t owns positions
+// t + 512 c, the first eight positions' descriptors in registers, keyframe 1 staged through LDS
+// 512 features at a time, one barrier per replayed feature).  The rotation histogram is filled
+// after the replay from the match12 entries of the node's own keyframe-1 features, which no other
+// workgroup writes (a feature of keyframe 1 is listed once).
+__global__ __launch_bounds__(kBowWideThreads) void k_bow_kf_nodes_wide(BowKfArgs a) {
+  __shared__ uint2 s_w[2][kBowWideWaves];
+  __shared__ uint4 s_dk[kBowWideTile][2];  // the tile's keyframe-1 descriptors
+  __shared__ int s_i1[kBowWideTile];       // and key indices (-1: no good MapPoint, skipped)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int4 tr = a.wide[blockIdx.x];
+  const int cand = tr.x, k = tr.y;
+  const BowKfView v1 = bow_kf_view(a.blk, a.kf1), v2 = bow_kf_view(a.blk, a.cand[cand]);
+  const int fb = v2.start[tr.z], fn = v2.start[tr.z + 1] - fb;  // <= kMaxMatchKeys (host)
+  const int nch = (fn + kBowWideThreads - 1) / kBowWideThreads;
+  int* row = a.match12 + (size_t)cand * (size_t)a.kf1.n;
+  int fi[kBowWideChunks];
+  // bit c: position tid + 512 c is matched, past the node's end or without a good MapPoint
+  uint32_t taken = 0;
+#pragma unroll
+  for (int c = 0; c < kBowWideChunks; c++) {
+    const int p = tid + kBowWideThreads * c;
+    fi[c] = p < fn ? v2.feat[fb + p] : 0;
+    if (p >= fn || !v2.ok[fi[c]]) taken |= 1u << c;
+  }
+  // a position past the end reads key 0's descriptor (fn > 0) and scores kBowNone
+  uint32_t dc[kBowWideRegChunks][8];
+#pragma unroll
+  for (int c = 0; c < kBowWideRegChunks; c++) load_desc8(v2.desc + 32 * (size_t)fi[c], dc[c]);
+  const int q0 = v1.start[k], q1 = v1.start[k + 1];
+  int nm = 0, par = 0;
+  for (int t0 = q0; t0 < q1; t0 += kBowWideTile) {
+    const int nt = min(kBowWideTile, q1 - t0);
+    __syncthreads();  // the previous tile is replayed
+    if (tid < nt) {
+      const int i = v1.feat[t0 + tid];
+      const bool ok = v1.ok[i] != 0;  // pMP1 != NULL and !isBad()
+      s_i1[tid] = ok ? i : -1;
+      if (ok) {
+        const uint4* d = reinterpret_cast<const uint4*>(v1.desc + 32 * (size_t)i);
+        s_dk[tid][0] = d[0];
+        s_dk[tid][1] = d[1];
+      }
+    }
+    __syncthreads();
+    for (int j = 0; j < nt; j++) {
+      const int i1 = __builtin_amdgcn_readfirstlane(s_i1[j]);
+      if (i1 < 0) continue;
+      const uint4 da = s_dk[j][0], db = s_dk[j][1];
+      const uint32_t dk[8] = {bow_uniform(da.x), bow_uniform(da.y), bow_uniform(da.z),
+                              bow_uniform(da.w), bow_uniform(db.x), bow_uniform(db.y),
+                              bow_uniform(db.z), bow_uniform(db.w)};
+      uint32_t k1 = kBowNone;  // thread-local smallest (dist << 16 | position)
+      int d2 = 256;            // thread-local second-smallest distance
+#pragma unroll
+      for (int c = 0; c < kBowWideRegChunks; c++) {
+        if (c >= nch) break;
+        bow_merge(bow_key(dk, dc[c], (taken >> c) & 1u, tid + kBowWideThreads * c), 256, k1, d2);
+      }
+#pragma unroll
+      for (int cb = kBowWideRegChunks; cb < kBowWideChunks; cb += kBowWideBatch) {
+        if (cb >= nch) break;
+        uint32_t df[kBowWideBatch][8];
+#pragma unroll
+        for (int b = 0; b < kBowWideBatch; b++)
+          load_desc8(v2.desc + 32 * (size_t)fi[cb + b], df[b]);
+#pragma unroll
+        for (int b = 0; b < kBowWideBatch; b++)
+          bow_merge(bow_key(dk, df[b], (taken >> (cb + b)) & 1u,
+                            tid + kBowWideThreads * (cb + b)), 256, k1, d2);
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t pk = (uint32_t)__shfl_xor((int)k1, o, 64);
+        const int pd = __shfl_xor(d2, o, 64);
+        bow_merge(pk, pd, k1, d2);
+      }
+      uint2* slot = s_w[par];
+      par ^= 1;
+      if (lane == 0) slot[wave] = make_uint2(k1, (uint32_t)d2);
+      __syncthreads();
+      uint32_t m1 = kBowNone;
+      int best2 = 256;
+#pragma unroll
+      for (int w = 0; w < kBowWideWaves; w++) {
+        const uint2 e = slot[w];
+        bow_merge(e.x, (int)e.y, m1, best2);
+      }
+      const int best1 = (int)(m1 >> 16);  // 256 when nothing is left
+      if (best1 >= TH_LOW || !((float)best1 < a.ratio * (float)best2)) continue;
+      const int p = (int)(m1 & 0xFFFFu);
+      if (tid == (p & (kBowWideThreads - 1))) {
+        int i2 = 0;
+#pragma unroll
+        for (int c = 0; c < kBowWideChunks; c++)
+          if (c == p / kBowWideThreads) i2 = fi[c];
+        taken |= 1u << (p / kBowWideThreads);
+        row[i1] = i2;
+      }
+      nm++;
+    }
+  }
+  if (tid == 0 && nm) atomicAdd(&a.counters[cand], nm);
+  if (a.check_orientation) {
+    __syncthreads();  // the workgroup's stores to its match12 entries
+    for (int q = q0 + tid; q < q1; q += kBowWideThreads) {
+      const int i1 = v1.feat[q];
+      const int i2 = row[i1];
+      if (i2 >= 0) bow_kf_hist_add(a.hist, cand, v1.angle[i1], v2.angle[i2]);
+    }
+  }
+}
+
+// the rotation-consistency filter (ORBmatcher.cc:1009-1027) and nmatches, one workgroup per
+// candidate
+__global__ __launch_bounds__(256) void k_bow_kf_rot(BowKfArgs a) {
+  __shared__ int s_ind[3], s_removed;
+  const int tid = threadIdx.x, cand = blockIdx.x;
+  const int* hist = a.hist + HISTO_LENGTH * cand;
+  if (tid == 0) {
+    s_removed = 0;
+    three_maxima([&](int h) { return a.check_orientation ? hist[h] : 0; }, s_ind);
+  }
+  __syncthreads();
+  int removed = 0;
+  if (a.check_orientation) {
+    const float* angle1 = reinterpret_cast<const float*>(a.blk + a.kf1.angle);
+    const float* angle2 = reinterpret_cast<const float*>(a.blk + a.cand[cand].angle);
+    int* row = a.match12 + (size_t)cand * (size_t)a.kf1.n;
+    for (int i1 = tid; i1 < a.kf1.n; i1 += blockDim.x) {
+      const int i2 = row[i1];
+      if (i2 < 0) continue;
+      const int bin = rot_bin(angle1[i1], angle2[i2]);
+      if (bin != s_ind[0] && bin != s_ind[1] && bin != s_ind[2]) {
+        row[i1] = -1;
+        removed++;
+      }
+    }
+  }
+  if (removed) atomicAdd(&s_removed, removed);
+  __syncthreads();
+  if (tid == 0) a.nmatches[cand] = a.counters[cand] - s_removed;
+}
+
+void bow_kf_wide_triples(int cand, const uint32_t* node1, int n_nodes1, const uint32_t* node2,
+                         const int* start2, int n_nodes2, std::vector<int4>& out) {
+  for (int i = 0, j = 0; i < n_nodes1 && j < n_nodes2;) {
+    if (node1[i] < node2[j]) {
+      i++;
+    } else if (node2[j] < node1[i]) {
+      j++;
+    } else {
+      if (start2[j + 1] - start2[j] > kBowMaxNodeFeatures) out.push_back(make_int4(cand, i, j, 0));
+      i++;
+      j++;
+    }
+  }
+}
+
+void launch_search_by_bow_keyframes(const BowKfArgs& a, hipStream_t st) {
+  if (a.n_cand <= 0) return;
+  const size_t rows = (size_t)a.n_cand * (size_t)a.kf1.n;
+  if (rows > 0) MMT_HIP(hipMemsetAsync(a.match12, 0xFF, sizeof(int) * rows, st));
+  MMT_HIP(hipMemsetAsync(a.hist, 0, sizeof(int) * HISTO_LENGTH * (size_t)a.n_cand, st));
+  MMT_HIP(hipMemsetAsync(a.counters, 0, sizeof(int) * (size_t)a.n_cand, st));
+  if (a.kf1.n_nodes > 0) {
+    hipLaunchKernelGGL(k_bow_kf_nodes, dim3((a.kf1.n_nodes + 3) / 4, a.n_cand), dim3(256), 0, st,
+                       a);
+    MMT_HIP(hipGetLastError());
+  }
+  if (a.n_wide > 0) {
+    hipLaunchKernelGGL(k_bow_kf_nodes_wide, dim3(a.n_wide), dim3(kBowWideThreads), 0, st, a);
+    MMT_HIP(hipGetLastError());
+  }
+  hipLaunchKernelGGL(k_bow_kf_rot, dim3(a.n_cand), dim3(256), 0, st, a);
+  MMT_HIP(hipGetLastError());
+}
+
 // ------------------------------------------------------------------------------ D1 edges
 // One 1024-thread workgroup: order-preserving compaction of the bound keys, 1024 keys per step.
 __global__ __launch_bounds__(1024) void k_map_edges(MapEdgeArgs a) {
