@@ -69,6 +69,11 @@
  *                          ORBmatcher.cc:1477-1701 (LoopClosing.cc:325)
  *   mmt_optimize_sim3   <- Optimizer::OptimizeSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale)
  *                          Optimizer.cc:3934-4129 (LoopClosing.cc:327), a batch of candidates
+ *   mmt_detect_loop     <- LoopClosing::DetectLoop LoopClosing.cc:105-231
+ *   mmt_detect_loop_candidates
+ *                       <- KeyFrameDatabase::DetectLoopCandidates KeyFrameDatabase.cc:76-197
+ *   mmt_loop_db_add / _erase
+ *                       <- KeyFrameDatabase::add / erase KeyFrameDatabase.cc:40-68
  *   mmt_destroy         <- System::Shutdown / delete
  */
 #ifndef MMT_H
@@ -871,6 +876,100 @@ int mmt_stereo_frame(mmt_ctx* ctx, const uint8_t* left, const uint8_t* right, in
                      mmt_kp* kps_right, uint8_t* desc_right, int cap_right, int* n_right,
                      float* uR, float* depth, int32_t* right_idx, int32_t* sem_label,
                      mmt_stereo_counters* counters);
+
+/* ---- Loop detection: keyframe database scores and loop candidates --------------------------------
+ * LoopClosing::DetectLoop (LoopClosing.cc:105-231) and KeyFrameDatabase::DetectLoopCandidates
+ * (KeyFrameDatabase.cc:76-197).  The context keeps every keyframe's BoW vector on the device; one
+ * kernel launch scores a stored vector against all of them (common words, first common word, the
+ * raw DBoW2 sum, added in word order: bit-identical to Vocabulary::score's loop), and the
+ * order-dependent rest runs on the host as the reference writes it.  The tracker does not call
+ * any of this.
+ *
+ * Most words of one stored vector; more is MMT_EINVAL (the query is staged in LDS: 12 bytes per
+ * word, 96 KiB at the bound, of the CU's 160 KiB). */
+#define MMT_LOOP_MAX_WORDS 8192
+
+/* DBoW2::BowVector: n (word, value) pairs, word strictly ascending. */
+typedef struct mmt_bow_vector {
+  int n;
+  const uint32_t* word;
+  const double* value;
+} mmt_bow_vector;
+
+/* The covisibility graph the detection reads, indexed by keyframe id (mnId), 0 .. n_kf-1.  The two
+ * lists differ in the reference: UpdateConnections keeps every keyframe that shares a map point
+ * in mConnectedKeyFrameWeights and only those at or above the threshold in the ordered list
+ * (KeyFrame.cc:289-367). */
+typedef struct mmt_covis_graph {
+  int n_kf;
+  const int32_t* ordered_start;    /* n_kf + 1 */
+  const int32_t* ordered;          /* mvpOrderedConnectedKeyFrames, weight descending:
+                                      GetVectorCovisibleKeyFrames; its first 10 =
+                                      GetBestCovisibilityKeyFrames(10) */
+  const int32_t* conn_start;       /* n_kf + 1 */
+  const int32_t* conn;             /* keys of mConnectedKeyFrameWeights = GetConnectedKeyFrames
+                                      (a set; any order) */
+  const uint8_t* bad;              /* isBad() */
+} mmt_covis_graph;
+
+typedef struct mmt_loop_result {
+  int32_t ran;           /* 0: the early exit (mnId < mLastLoopKFid + 10), nothing was scored   */
+  float min_score;       /* minScore over the non-bad covisible keyframes (1 without one)      */
+  int32_t n_candidates;  /* vpCandidateKFs.size()                                               */
+  int32_t n_enough;      /* mvpEnoughConsistentCandidates.size()                                */
+  int32_t n_groups;      /* mvConsistentGroups.size() after the call                            */
+} mmt_loop_result;
+
+typedef struct mmt_loop_store_stats {
+  int32_t n_stored;        /* vectors on the device                                            */
+  int32_t n_members;       /* keyframes in the database                                        */
+  int64_t word_capacity;   /* elements the device word array holds                             */
+  int64_t value_capacity;  /* elements the device value array holds                            */
+  int32_t word_grown;      /* times the word array was reallocated and copied                  */
+  int32_t value_grown;     /* the same for the value array                                     */
+} mmt_loop_store_stats;
+
+/* Every call below returns MMT_EINVAL for an unknown keyframe id, an id outside the graph, a
+ * vector that is not strictly ascending or too long, and an output buffer that is too small.
+ *
+ * mmt_loop_reset: empties the store, the database and the consistency groups; scoring is the
+ *   vocabulary's field (0: L1, 1: L2; TemplatedVocabulary has no other that Vocabulary::score
+ *   implements here).
+ * mmt_loop_set_bow: KeyFrame::ComputeBoW's mBowVec onto the device, once per keyframe id (a second
+ *   call for the same id is MMT_EINVAL; a stored vector never changes).
+ * mmt_loop_db_add / _erase: KeyFrameDatabase::add / erase.  A member is added once (a second add
+ *   is MMT_EINVAL); erasing a non-member does nothing.  The vector stays stored after an erase, as
+ *   the keyframe keeps its mBowVec: minScore still reads it.
+ * mmt_loop_scores (probe): the kernel's outputs for every stored vector against kf_id's, in
+ *   storage order, with the finished double score (Vocabulary::score) and the keyframe ids.
+ * mmt_detect_loop_candidates: DetectLoopCandidates(kf_id, min_score) in the reference's order; the
+ *   database and the groups are not touched.
+ * mmt_detect_loop: DetectLoop for keyframe kf_id (not yet a database member) with mLastLoopKFid =
+ *   last_loop_kf_id and mnCovisibilityConsistencyTh = consistency_th (the reference: 3).  cand_out
+ *   receives vpCandidateKFs, enough_out mvpEnoughConsistentCandidates (cap entries each); the
+ *   keyframe is added to the database as the reference does on every path.  The reference's
+ *   DetectLoop returns false in this fork whatever the list holds (LoopClosing.cc:225); acting on
+ *   result->n_enough > 0 is the caller's business.  A non-bad covisible keyframe with no stored
+ *   vector is MMT_EINVAL.  On an error nothing has changed.
+ * mmt_loop_groups_read: mvConsistentGroups as a CSR of ascending member ids (group_start:
+ *   n_groups + 1 entries) plus the consistency counters.
+ * One kernel launch and one read-back (16 bytes per stored vector) per scores / candidates /
+ * detect call; nothing but the slot index of kf_id goes up. */
+int mmt_loop_reset(mmt_ctx* ctx, int scoring);
+int mmt_loop_set_bow(mmt_ctx* ctx, int32_t kf_id, const mmt_bow_vector* v);
+int mmt_loop_db_add(mmt_ctx* ctx, int32_t kf_id);
+int mmt_loop_db_erase(mmt_ctx* ctx, int32_t kf_id);
+int mmt_loop_scores(mmt_ctx* ctx, int32_t kf_id, int32_t* common, int32_t* first, double* sum,
+                    double* score, int32_t* ids, int cap, int* n_out);
+int mmt_detect_loop_candidates(mmt_ctx* ctx, int32_t kf_id, float min_score,
+                               const mmt_covis_graph* graph, int32_t* cand_out, int cap,
+                               int* n_out);
+int mmt_detect_loop(mmt_ctx* ctx, int32_t kf_id, int32_t last_loop_kf_id, int consistency_th,
+                    const mmt_covis_graph* graph, mmt_loop_result* result, int32_t* cand_out,
+                    int32_t* enough_out, int cap);
+int mmt_loop_groups_read(mmt_ctx* ctx, int32_t* group_start, int32_t* members, int32_t* counters,
+                         int cap_groups, int cap_members, int* n_groups, int* n_members);
+int mmt_loop_stats(mmt_ctx* ctx, mmt_loop_store_stats* out);
 
 /* Upper bound on keypoints per frame: the sum over levels of max(quota, 4 * nIni) + 8 slots, where
  * DistributeOctTree keeps at most max(quota + 2, 4 * nIni) keys. */

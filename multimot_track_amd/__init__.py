@@ -212,6 +212,62 @@ class MmtBowKeyFrame(ctypes.Structure):
                 ("mp_valid", ctypes.c_void_p), ("fv", MmtFeatureVector)]
 
 
+class MmtBowVector(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("word", ctypes.c_void_p), ("value", ctypes.c_void_p)]
+
+
+class MmtCovisGraph(ctypes.Structure):
+    _fields_ = [("n_kf", ctypes.c_int), ("ordered_start", ctypes.c_void_p),
+                ("ordered", ctypes.c_void_p), ("conn_start", ctypes.c_void_p),
+                ("conn", ctypes.c_void_p), ("bad", ctypes.c_void_p)]
+
+
+class MmtLoopResult(ctypes.Structure):
+    _fields_ = [("ran", ctypes.c_int32), ("min_score", ctypes.c_float),
+                ("n_candidates", ctypes.c_int32), ("n_enough", ctypes.c_int32),
+                ("n_groups", ctypes.c_int32)]
+
+
+class MmtLoopStoreStats(ctypes.Structure):
+    _fields_ = [("n_stored", ctypes.c_int32), ("n_members", ctypes.c_int32),
+                ("word_capacity", ctypes.c_int64), ("value_capacity", ctypes.c_int64),
+                ("word_grown", ctypes.c_int32), ("value_grown", ctypes.c_int32)]
+
+
+MMT_LOOP_MAX_WORDS = 8192  # include/mmt.h
+
+
+def _covis_graph(graph, keep):
+    """graph: dict(ordered=[list per keyframe id], conn=[list per keyframe id], bad=[n_kf]) ->
+    mmt_covis_graph (CSR)."""
+    n = len(graph["bad"])
+    if len(graph["ordered"]) != n or len(graph["conn"]) != n:
+        raise ValueError("the graph's lists follow its keyframes")
+
+    def csr(rows):
+        start = np.zeros(n + 1, np.int32)
+        if n:
+            start[1:] = np.cumsum([len(r) for r in rows])
+        flat = np.ascontiguousarray(
+            np.concatenate([np.asarray(r, np.int32).reshape(-1) for r in rows])
+            if n else np.zeros(0, np.int32), np.int32)
+        if flat.size == 0:
+            flat = np.zeros(1, np.int32)
+        return start, flat
+
+    os_, ol = csr(graph["ordered"])
+    cs, cl = csr(graph["conn"])
+    bad = np.ascontiguousarray(np.asarray(graph["bad"], np.uint8).reshape(-1))
+    if bad.size == 0:
+        bad = np.zeros(1, np.uint8)
+    keep += [os_, ol, cs, cl, bad]
+    g = MmtCovisGraph()
+    g.n_kf = n
+    g.ordered_start, g.ordered = os_.ctypes.data, ol.ctypes.data
+    g.conn_start, g.conn, g.bad = cs.ctypes.data, cl.ctypes.data, bad.ctypes.data
+    return g
+
+
 class MmtKeyFramePoints(ctypes.Structure):
     _fields_ = [("m", ctypes.c_int), ("Xw", ctypes.c_void_p), ("min_dist", ctypes.c_void_p),
                 ("max_dist", ctypes.c_void_p), ("desc", ctypes.c_void_p),
@@ -383,6 +439,18 @@ def lib():
         L.mmt_bow_counters_read.argtypes = [vp, ctypes.POINTER(MmtBowCounters)]
         L.mmt_set_deferred_objects.argtypes = [vp, i32]
         L.mmt_flush_objects.argtypes = [vp, vp, vp, i32, i32, vp]
+        L.mmt_loop_reset.argtypes = [vp, i32]
+        L.mmt_loop_set_bow.argtypes = [vp, ctypes.c_int32, ctypes.POINTER(MmtBowVector)]
+        L.mmt_loop_db_add.argtypes = [vp, ctypes.c_int32]
+        L.mmt_loop_db_erase.argtypes = [vp, ctypes.c_int32]
+        L.mmt_loop_scores.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp, vp, i32, vp]
+        L.mmt_detect_loop_candidates.argtypes = [vp, ctypes.c_int32, ctypes.c_float,
+                                                 ctypes.POINTER(MmtCovisGraph), vp, i32, vp]
+        L.mmt_detect_loop.argtypes = [vp, ctypes.c_int32, ctypes.c_int32, i32,
+                                      ctypes.POINTER(MmtCovisGraph),
+                                      ctypes.POINTER(MmtLoopResult), vp, vp, i32]
+        L.mmt_loop_groups_read.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
+        L.mmt_loop_stats.argtypes = [vp, ctypes.POINTER(MmtLoopStoreStats)]
         _LIB = L
     return _LIB
 
@@ -996,6 +1064,96 @@ class Context:
                      t=np.array(R[i].t[:], np.float64), kept=kept[:n].astype(bool),
                      chi2=chi2[:n].copy(), stats=list(R[i].stats))
                 for i, (n, kept, chi2) in enumerate(outs)]
+
+    # ---- loop detection (LoopClosing::DetectLoop, KeyFrameDatabase) ----
+    def loop_reset(self, scoring=0):
+        """Empties the device store of BoW vectors, the keyframe database and the consistency
+        groups; scoring 0: L1, 1: L2 (mmt_loop_reset)."""
+        self._check(lib().mmt_loop_reset(self._h, int(scoring)))
+
+    def loop_set_bow(self, kf_id, word, value):
+        """KeyFrame::ComputeBoW's mBowVec of keyframe kf_id onto the device, once per id: word
+        strictly ascending, at most MMT_LOOP_MAX_WORDS (mmt_loop_set_bow)."""
+        w = np.ascontiguousarray(word, np.uint32).reshape(-1)
+        x = np.ascontiguousarray(value, np.float64).reshape(-1)
+        if len(w) != len(x):
+            raise ValueError("one value per word")
+        v = MmtBowVector(len(w), w.ctypes.data, x.ctypes.data)
+        self._check(lib().mmt_loop_set_bow(self._h, int(kf_id), ctypes.byref(v)))
+
+    def loop_db_add(self, kf_id):
+        """KeyFrameDatabase::add (mmt_loop_db_add)."""
+        self._check(lib().mmt_loop_db_add(self._h, int(kf_id)))
+
+    def loop_db_erase(self, kf_id):
+        """KeyFrameDatabase::erase (mmt_loop_db_erase)."""
+        self._check(lib().mmt_loop_db_erase(self._h, int(kf_id)))
+
+    def loop_stats(self):
+        """Stored vectors, database members, the device arrays' capacities and how often each has
+        grown (mmt_loop_stats)."""
+        st = MmtLoopStoreStats()
+        self._check(lib().mmt_loop_stats(self._h, ctypes.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in MmtLoopStoreStats._fields_}
+
+    def loop_scores(self, kf_id):
+        """k_loop_score's outputs for every stored vector against keyframe kf_id's, in storage
+        order: dict(ids, common, first (INT_MAX without a common word), sum (the raw DBoW2 sum),
+        score (Vocabulary::score)) (mmt_loop_scores)."""
+        cap = max(self.loop_stats()["n_stored"], 1)
+        common = np.zeros(cap, np.int32)
+        first = np.zeros(cap, np.int32)
+        sm = np.zeros(cap, np.float64)
+        score = np.zeros(cap, np.float64)
+        ids = np.zeros(cap, np.int32)
+        n = ctypes.c_int(0)
+        self._check(lib().mmt_loop_scores(self._h, int(kf_id), _p(common), _p(first), _p(sm),
+                                          _p(score), _p(ids), cap, ctypes.byref(n)))
+        n = n.value
+        return dict(ids=ids[:n], common=common[:n], first=first[:n], sum=sm[:n], score=score[:n])
+
+    def detect_loop_candidates(self, kf_id, min_score, graph):
+        """KeyFrameDatabase::DetectLoopCandidates(kf_id, min_score) -> keyframe ids in the
+        reference's order.  graph: dict(ordered, conn (a list of ids per keyframe id), bad)
+        (mmt_detect_loop_candidates)."""
+        keep = []
+        g = _covis_graph(graph, keep)
+        cap = max(self.loop_stats()["n_members"], 1)
+        out = np.zeros(cap, np.int32)
+        n = ctypes.c_int(0)
+        self._check(lib().mmt_detect_loop_candidates(self._h, int(kf_id), float(min_score),
+                                                     ctypes.byref(g), _p(out), cap,
+                                                     ctypes.byref(n)))
+        return out[:n.value].tolist()
+
+    def detect_loop(self, kf_id, last_loop_kf_id, graph, consistency_th=3):
+        """LoopClosing::DetectLoop for keyframe kf_id -> dict(ran, min_score (float32),
+        candidates, enough (the enough-consistent candidates), n_groups) (mmt_detect_loop)."""
+        keep = []
+        g = _covis_graph(graph, keep)
+        cap = max(self.loop_stats()["n_members"], 1)
+        cand = np.zeros(cap, np.int32)
+        enough = np.zeros(cap, np.int32)
+        r = MmtLoopResult()
+        self._check(lib().mmt_detect_loop(self._h, int(kf_id), int(last_loop_kf_id),
+                                          int(consistency_th), ctypes.byref(g), ctypes.byref(r),
+                                          _p(cand), _p(enough), cap))
+        return dict(ran=bool(r.ran), min_score=np.float32(r.min_score),
+                    candidates=cand[:r.n_candidates].tolist(),
+                    enough=enough[:r.n_enough].tolist(), n_groups=int(r.n_groups))
+
+    def loop_groups(self):
+        """mvConsistentGroups: [(sorted member ids, consistency counter)] (mmt_loop_groups_read)."""
+        ng, nm = ctypes.c_int(0), ctypes.c_int(0)
+        lib().mmt_loop_groups_read(self._h, None, None, None, 0, 0, ctypes.byref(ng),
+                                   ctypes.byref(nm))  # sizes only (EINVAL unless both are 0)
+        start = np.zeros(ng.value + 1, np.int32)
+        mem = np.zeros(max(nm.value, 1), np.int32)
+        cnt = np.zeros(max(ng.value, 1), np.int32)
+        self._check(lib().mmt_loop_groups_read(self._h, _p(start), _p(mem), _p(cnt), ng.value,
+                                               max(nm.value, 1), ctypes.byref(ng),
+                                               ctypes.byref(nm)))
+        return [(mem[start[i]:start[i + 1]].tolist(), int(cnt[i])) for i in range(ng.value)]
 
     def local_bundle_adjustment(self, P):
         """Optimizer::LocalBundleAdjustment's solve on a problem dict (keys T, fixed, X, pt, kf,

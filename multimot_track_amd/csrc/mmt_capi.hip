@@ -733,6 +733,119 @@ int mmt_map_dump(mmt_ctx* ctx, int32_t* sizes, const mmt_map_dump_arrays* out) {
   });
 }
 
+// ---- loop detection (LoopClosing::DetectLoop, KeyFrameDatabase; mmt_loop.hip, mmt_loopdetect.cpp)
+int mmt_loop_reset(mmt_ctx* ctx, int scoring) {
+  if (!ctx) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (scoring != 0 && scoring != 1) throw ArgError("mmt_loop_reset: scoring is 0 (L1) or 1 (L2)");
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    MMT_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->loop.reset();
+    ctx->loopdet.reset(scoring);
+  });
+}
+
+int mmt_loop_set_bow(mmt_ctx* ctx, int32_t kf_id, const mmt_bow_vector* v) {
+  if (!ctx || !v) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    ctx->loop.set_bow(kf_id, *v, ctx->stream);
+  });
+}
+
+int mmt_loop_db_add(mmt_ctx* ctx, int32_t kf_id) {
+  if (!ctx) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (ctx->loop.table.find(kf_id) < 0) throw ArgError("mmt_loop_db_add: unknown keyframe id");
+    if (!ctx->loop.table.db_add(kf_id))
+      throw ArgError("mmt_loop_db_add: the keyframe is in the database already");
+  });
+}
+
+int mmt_loop_db_erase(mmt_ctx* ctx, int32_t kf_id) {
+  if (!ctx) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (!ctx->loop.table.db_erase(kf_id)) throw ArgError("mmt_loop_db_erase: unknown keyframe id");
+  });
+}
+
+static void copy_ids(const std::vector<int32_t>& v, int32_t* out, int cap, const char* what) {
+  if ((int)v.size() > cap || (!v.empty() && !out))
+    throw ArgError(std::string(what) + ": output buffer too small");
+  if (!v.empty()) memcpy(out, v.data(), sizeof(int32_t) * v.size());
+}
+
+int mmt_detect_loop_candidates(mmt_ctx* ctx, int32_t kf_id, float min_score,
+                               const mmt_covis_graph* graph, int32_t* cand_out, int cap,
+                               int* n_out) {
+  if (!ctx || !graph || !n_out || cap < 0) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    if (kf_id < 0 || kf_id >= graph->n_kf)
+      throw ArgError("mmt_detect_loop_candidates: keyframe id outside the graph");
+    const std::vector<mmt::LoopScore>& sc =
+        ctx->loop.score(kf_id, ctx->loopdet.scoring(), ctx->stream);
+    std::vector<int32_t> cand;
+    if (!ctx->loopdet.candidates(ctx->loop.table, sc.data(), kf_id, min_score, *graph, cand))
+      throw ArgError("mmt_detect_loop_candidates: " + ctx->loopdet.error());
+    *n_out = (int)cand.size();
+    copy_ids(cand, cand_out, cap, "mmt_detect_loop_candidates");
+  });
+}
+
+int mmt_detect_loop(mmt_ctx* ctx, int32_t kf_id, int32_t last_loop_kf_id, int consistency_th,
+                    const mmt_covis_graph* graph, mmt_loop_result* result, int32_t* cand_out,
+                    int32_t* enough_out, int cap) {
+  if (!ctx || !graph || !result || cap < 0) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    mmt::LoopSlotTable& T = ctx->loop.table;
+    const int slot = T.find(kf_id);
+    if (slot < 0) throw ArgError("mmt_detect_loop: unknown keyframe id");
+    if (T.slots[slot].member) throw ArgError("mmt_detect_loop: the keyframe is in the database");
+    const bool early = mmt::LoopDetector::early_exit(kf_id, last_loop_kf_id);
+    if (!early && (kf_id < 0 || kf_id >= graph->n_kf))
+      throw ArgError("mmt_detect_loop: keyframe id outside the graph");
+    const mmt::LoopScore* sc = nullptr;
+    if (!early) sc = ctx->loop.score(kf_id, ctx->loopdet.scoring(), ctx->stream).data();
+    // detect() refuses more than `cap` candidates before it changes the database or the groups
+    std::vector<int32_t> cand, enough;
+    if (!ctx->loopdet.detect(T, sc, kf_id, last_loop_kf_id, consistency_th, *graph,
+                             (cand_out && enough_out) ? cap : 0, *result, cand, enough))
+      throw ArgError("mmt_detect_loop: " + ctx->loopdet.error());
+    copy_ids(cand, cand_out, cap, "mmt_detect_loop");
+    copy_ids(enough, enough_out, cap, "mmt_detect_loop");
+  });
+}
+
+int mmt_loop_groups_read(mmt_ctx* ctx, int32_t* group_start, int32_t* members, int32_t* counters,
+                         int cap_groups, int cap_members, int* n_groups, int* n_members) {
+  if (!ctx || !n_groups || !n_members || cap_groups < 0 || cap_members < 0) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    const auto& G = ctx->loopdet.groups();
+    size_t nm = 0;
+    for (const auto& g : G) nm += g.first.size();
+    *n_groups = (int)G.size();
+    *n_members = (int)nm;
+    if ((int)G.size() > cap_groups || nm > (size_t)cap_members)
+      throw ArgError("mmt_loop_groups_read: output buffer too small");
+    if (!group_start || (!G.empty() && !counters) || (nm > 0 && !members))
+      throw ArgError("mmt_loop_groups_read: null output arrays");
+    int32_t at = 0;
+    for (size_t i = 0; i < G.size(); i++) {
+      group_start[i] = at;
+      counters[i] = G[i].second;
+      for (int32_t m : G[i].first) members[at++] = m;
+    }
+    group_start[G.size()] = at;
+  });
+}
+
+int mmt_loop_stats(mmt_ctx* ctx, mmt_loop_store_stats* out) {
+  if (!ctx || !out) return MMT_EINVAL;
+  return guard(ctx, [&] { ctx->loop.stats(*out); });
+}
+
 long mmt_debug_fetch(mmt_ctx* ctx, int what, int frame, void* out, size_t cap) {
   if (!ctx || !out) return MMT_EINVAL;
   long r = 0;

@@ -576,6 +576,31 @@ int mmt_bow_transform(mmt_ctx* ctx, const uint8_t* desc, int n, int levelsup, ui
   });
 }
 
+// The probe of k_loop_score (mmt_loop.hip): its records for every stored vector against kf_id's,
+// in storage order, and the score Vocabulary::score finishes from the sum.
+int mmt_loop_scores(mmt_ctx* ctx, int32_t kf_id, int32_t* common, int32_t* first, double* sum,
+                    double* score, int32_t* ids, int cap, int* n_out) {
+  if (!ctx || !n_out || cap < 0) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    const auto& slots = ctx->loop.table.slots;
+    if (ctx->loop.table.find(kf_id) < 0) throw ArgError("mmt_loop_scores: unknown keyframe id");
+    const int n = (int)slots.size();
+    *n_out = n;
+    if (n > cap || !common || !first || !sum || !score || !ids)
+      throw ArgError("mmt_loop_scores: output buffer too small");
+    const int scoring = ctx->loopdet.scoring();
+    const std::vector<mmt::LoopScore>& sc = ctx->loop.score(kf_id, scoring, ctx->stream);
+    for (int k = 0; k < n; k++) {
+      common[k] = sc[k].common;
+      first[k] = sc[k].first;
+      sum[k] = sc[k].sum;
+      score[k] = mmt::loop_finish_score(sc[k].sum, scoring);
+      ids[k] = slots[k].kf_id;
+    }
+  });
+}
+
 int mmt_search_by_bow(mmt_ctx* ctx, const mmt_bow_keyframe* kf, int n_cur, const mmt_kp* cur_kps,
                       const uint8_t* cur_desc, const mmt_feature_vector* cur_fv, float nn_ratio,
                       int check_orientation, int32_t* match_out, int* nmatches) {

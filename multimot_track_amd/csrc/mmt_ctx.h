@@ -7,6 +7,7 @@
 #include "mmt_ba.h"
 #include "mmt_bow.h"
 #include "mmt_internal.h"
+#include "mmt_loop.h"
 #include "mmt_stereo.h"
 #include "mmt_tracker.h"
 
@@ -36,6 +37,8 @@ struct mmt_ctx {
   int t_frames = 0;  // frames the t_* staging buffers hold
   std::deque<mmt::FrameOut> flushed;  // mmt_flush_objects records not yet handed out
   std::unique_ptr<mmt::Vocabulary> voc;  // mmt_load_vocabulary (System's ORB vocabulary)
+  mmt::LoopStore loop;        // mmt_loop_*: the keyframes' BoW vectors on the device, the database
+  mmt::LoopDetector loopdet;  // mmt_detect_loop: mvConsistentGroups
 };
 
 // Every C-ABI entry point runs its body through this: internal exceptions become an errno-style
