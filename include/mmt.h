@@ -786,6 +786,65 @@ int mmt_map_dump(mmt_ctx* ctx, int32_t* sizes, const mmt_map_dump_arrays* out);
 int mmt_frame_samples(mmt_ctx* ctx, float* static_xy, int static_cap, int* n_static,
                       float* obj_xy, int32_t* obj_label, int obj_cap, int* n_obj);
 
+/* ---- Object front end probes: one stage of the per-frame object path run alone on host arrays.
+ * W and H are arguments (not the context's configuration); maps are W x H row-major, flow maps
+ * W x H x 2 floats, masks int32.  Sample outputs hold `cap` entries; entries the stage does not
+ * write come back with all bytes 0xFF. */
+
+/* A2 (Tracking.cc:447-465): cvtColor(RGB2GRAY) on the colour bytes and disparity -> depth,
+ * depth = bf / (float)(d / 256.0), for nframes frames of npix pixels in one launch.  Pitches are
+ * per frame, in elements of the array (bytes for bgr and gray); gray and depth are read-write:
+ * their padding keeps the caller's bytes. */
+int mmt_gray_depth(mmt_ctx* ctx, const uint8_t* bgr, size_t bgr_pitch, const uint16_t* disp256,
+                   size_t disp_pitch, int npix, int nframes, float bf, uint8_t* gray,
+                   size_t gray_pitch, float* depth, size_t depth_pitch);
+
+/* B2 (Frame.cc:228-324): the static ORB keys kept through the flow, in key order:
+ * mvSiftKeysTmp, mvCorres, mvFlowNext, mvSiftDepthTmp; *count = min(kept, cap).  Keys must lie
+ * inside the image (the maps are read at the truncated key). */
+int mmt_static_samples(mmt_ctx* ctx, const mmt_kp* kps, int n, const float* depth,
+                       const float* flow, const int32_t* mask, int W, int H, int cap,
+                       float* keys_out, float* corres_out, float* flow_out, float* depth_out,
+                       int* count);
+
+/* B1 (Frame.cc:188-217): the semi-dense object samples of every 4th row and column, row-major:
+ * mvObjKeys, mvObjCorres, mvObjFlowNext, mvObjDepth, vSemObjLabel; *count = min(kept, cap). */
+int mmt_object_samples(mmt_ctx* ctx, const float* depth, const float* flow, const int32_t* mask,
+                       int W, int H, int cap, float* keys_out, float* corres_out, float* flow_out,
+                       float* depth_out, int32_t* label_out, int* count);
+
+/* B4 (Tracking.cc:487-578): the last frame's correspondences become the current frame's keys;
+ * depth (static: -1 unless > 0) and depth and label (object: 0.1 and 0 outside the image) are read
+ * at the std::round coordinates, inside meaning 0 < round(u) < W and 0 < round(v) < H. */
+int mmt_sample_handoff(mmt_ctx* ctx, const float* last_corres, int ns, const float* last_obj_corres,
+                       int no, const float* depth, const int32_t* mask, int W, int H,
+                       float* skeys_out, float* sdepth_out, float* okeys_out, float* odepth_out,
+                       int32_t* olabel_out, int* ns_out, int* no_out);
+
+/* B6 + B7 statistics (GetSceneFlowObj, Tracking.cc:4007-4093, with Frame::UnprojectStereoObject,
+ * Frame.cc:1118-1152; the Posi lists and the per-object counters of Tracking.cc:1396-1536; the
+ * last-label counts of Tracking.cc:1573-1585).  Sample i has its current key, depth and label and
+ * its last-frame ones.  obj_label_out n: vObjLabel after GetSceneFlowObj (-1, or -2 where the
+ * reference leaves its initial value); members_out 16 x max(n, 1): label l's sample indices
+ * ascending in row l (Posi); stats_out 16 x 8 words per label: cnt, bcnt (samples in the boundary
+ * band), sfcnt (scene flow under 0.12), members, depth_sum (a float: the samples' current depths
+ * added in index order), three unused; hist_out 16 x 16: [current label][last label] counts.
+ * A current or last label above 15 sets *err_out and fails the call with MMT_EINVAL. */
+typedef struct mmt_obj_group_problem {
+  int n;
+  const float* cur_keys;   /* n x 2 */
+  const float* cur_depth;
+  const int32_t* cur_label;
+  const float* last_keys;  /* n x 2 */
+  const float* last_depth;
+  const int32_t* last_label;
+  float Tcur[16], Tlast[16]; /* row-major Tcw of the current and the last frame */
+  float fx, fy, cx, cy;
+  int W, H;
+} mmt_obj_group_problem;
+int mmt_object_groups(mmt_ctx* ctx, const mmt_obj_group_problem* problem, int32_t* obj_label_out,
+                      int32_t* members_out, int32_t* stats_out, int32_t* hist_out, int* err_out);
+
 /* Stage timing with HIP events on the launch stream (no reference counterpart: measurement
  * hook for bench.py).  orb_ms sums the batched ORB launch sequences of the tracked chunks. */
 typedef struct mmt_profile {

@@ -70,6 +70,15 @@ class MmtPoseOptProblem(ctypes.Structure):
                 ("cy", ctypes.c_float), ("bf", ctypes.c_float)]
 
 
+class MmtObjGroupProblem(ctypes.Structure):
+    _fields_ = [("n", ctypes.c_int), ("cur_keys", ctypes.c_void_p), ("cur_depth", ctypes.c_void_p),
+                ("cur_label", ctypes.c_void_p), ("last_keys", ctypes.c_void_p),
+                ("last_depth", ctypes.c_void_p), ("last_label", ctypes.c_void_p),
+                ("Tcur", ctypes.c_float * 16), ("Tlast", ctypes.c_float * 16),
+                ("fx", ctypes.c_float), ("fy", ctypes.c_float), ("cx", ctypes.c_float),
+                ("cy", ctypes.c_float), ("W", ctypes.c_int), ("H", ctypes.c_int)]
+
+
 class MmtMatchFrame(ctypes.Structure):
     _fields_ = [("n", ctypes.c_int), ("kps", ctypes.c_void_p), ("desc", ctypes.c_void_p),
                 ("depth", ctypes.c_void_p), ("Tcw", ctypes.c_float * 16)]
@@ -451,6 +460,11 @@ def lib():
                                       ctypes.POINTER(MmtLoopResult), vp, vp, i32]
         L.mmt_loop_groups_read.argtypes = [vp, vp, vp, vp, i32, i32, vp, vp]
         L.mmt_loop_stats.argtypes = [vp, ctypes.POINTER(MmtLoopStoreStats)]
+        L.mmt_gray_depth.argtypes = [vp, vp, sz, vp, sz, i32, i32, ctypes.c_float, vp, sz, vp, sz]
+        L.mmt_static_samples.argtypes = [vp, vp, i32, vp, vp, vp, i32, i32, i32] + [vp] * 5
+        L.mmt_object_samples.argtypes = [vp, vp, vp, vp, i32, i32, i32] + [vp] * 6
+        L.mmt_sample_handoff.argtypes = [vp, vp, i32, vp, i32, vp, vp, i32, i32] + [vp] * 7
+        L.mmt_object_groups.argtypes = [vp, ctypes.POINTER(MmtObjGroupProblem)] + [vp] * 5
         _LIB = L
     return _LIB
 
@@ -702,6 +716,120 @@ class Context:
         self._check(lib().mmt_pose_optimization(self._h, ctypes.byref(pr), _p(pose), _p(out),
                                                 ctypes.byref(ninl)))
         return ninl.value, pose.reshape(4, 4), out[:n].astype(bool)
+
+    # ---- object front end probes (A2, B1, B2, B4, B6 + B7 statistics) ----------------------
+    def gray_depth(self, bgr, disp, bf, pitch_pad=(0, 0, 0, 0), fill=0xA5):
+        """A2: cvtColor(RGB2GRAY) + disparity -> depth for F frames in one launch.  bgr F x H x W
+        x 3 (or H x W x 3) u8, disp F x H x W u16.  pitch_pad: elements added to the per-frame
+        pitch of bgr, disp, gray, depth.  Returns (gray F x H x W, depth F x H x W, gray padding,
+        depth padding as raw bytes: still `fill` when the launch kept inside its frames)."""
+        bgr = np.asarray(bgr, np.uint8)
+        disp = np.asarray(disp, np.uint16)
+        if bgr.ndim == 3:
+            bgr, disp = bgr[None], disp[None]
+        F, H, W = disp.shape
+        npix = W * H
+        pb, pd, pg, pz = (int(x) for x in pitch_pad)
+        B = np.full((F, 3 * npix + pb), fill, np.uint8)
+        D = np.full((F, npix + pd), fill * 257, np.uint16)
+        G = np.full((F, npix + pg), fill, np.uint8)
+        Z = np.full((F, npix + pz), fill * 0x01010101, np.uint32).view(np.float32)
+        B[:, :3 * npix] = bgr.reshape(F, -1)
+        D[:, :npix] = disp.reshape(F, -1)
+        self._check(lib().mmt_gray_depth(self._h, _p(B), B.shape[1], _p(D), D.shape[1], npix, F,
+                                         bf, _p(G), G.shape[1], _p(Z), Z.shape[1]))
+        return (G[:, :npix].reshape(F, H, W), Z[:, :npix].reshape(F, H, W),
+                G[:, npix:].copy(), Z[:, npix:].copy().view(np.uint8))
+
+    @staticmethod
+    def _maps(depth, flow, mask):
+        depth = np.ascontiguousarray(depth, np.float32)
+        H, W = depth.shape
+        flow = np.ascontiguousarray(flow, np.float32).reshape(H, W, 2)
+        mask = np.ascontiguousarray(mask, np.int32).reshape(H, W)
+        return depth, flow, mask, W, H
+
+    def static_samples(self, kps, depth, flow, mask, cap):
+        """B2: dict(keys, corres, flow cap x 2, depth cap, count); entries past count keep the
+        probe's fill (all bytes 0xFF)."""
+        kps = np.ascontiguousarray(kps, KP_DTYPE)
+        depth, flow, mask, W, H = self._maps(depth, flow, mask)
+        m = max(cap, 1)
+        keys, cor, fl = (np.zeros((m, 2), np.float32) for _ in range(3))
+        dep = np.zeros(m, np.float32)
+        cnt = ctypes.c_int(-1)
+        self._check(lib().mmt_static_samples(self._h, _p(kps), len(kps), _p(depth), _p(flow),
+                                             _p(mask), W, H, cap, _p(keys), _p(cor), _p(fl),
+                                             _p(dep), ctypes.byref(cnt)))
+        return dict(keys=keys[:cap], corres=cor[:cap], flow=fl[:cap], depth=dep[:cap],
+                    count=cnt.value)
+
+    def object_samples(self, depth, flow, mask, cap):
+        """B1: dict(keys, corres, flow cap x 2, depth, label cap, count)."""
+        depth, flow, mask, W, H = self._maps(depth, flow, mask)
+        m = max(cap, 1)
+        keys, cor, fl = (np.zeros((m, 2), np.float32) for _ in range(3))
+        dep = np.zeros(m, np.float32)
+        lab = np.zeros(m, np.int32)
+        cnt = ctypes.c_int(-1)
+        self._check(lib().mmt_object_samples(self._h, _p(depth), _p(flow), _p(mask), W, H, cap,
+                                             _p(keys), _p(cor), _p(fl), _p(dep), _p(lab),
+                                             ctypes.byref(cnt)))
+        return dict(keys=keys[:cap], corres=cor[:cap], flow=fl[:cap], depth=dep[:cap],
+                    label=lab[:cap], count=cnt.value)
+
+    def sample_handoff(self, last_corres, last_obj_corres, depth, mask):
+        """B4: dict(skeys, sdepth, okeys, odepth, olabel, ns, no)."""
+        lc = np.ascontiguousarray(last_corres, np.float32).reshape(-1, 2)
+        lo = np.ascontiguousarray(last_obj_corres, np.float32).reshape(-1, 2)
+        depth = np.ascontiguousarray(depth, np.float32)
+        H, W = depth.shape
+        mask = np.ascontiguousarray(mask, np.int32).reshape(H, W)
+        ns, no = len(lc), len(lo)
+        sk, ok = np.zeros((max(ns, 1), 2), np.float32), np.zeros((max(no, 1), 2), np.float32)
+        sd, od = np.zeros(max(ns, 1), np.float32), np.zeros(max(no, 1), np.float32)
+        ol = np.zeros(max(no, 1), np.int32)
+        a, b = ctypes.c_int(-1), ctypes.c_int(-1)
+        self._check(lib().mmt_sample_handoff(self._h, _p(lc), ns, _p(lo), no, _p(depth), _p(mask),
+                                             W, H, _p(sk), _p(sd), _p(ok), _p(od), _p(ol),
+                                             ctypes.byref(a), ctypes.byref(b)))
+        return dict(skeys=sk[:ns], sdepth=sd[:ns], okeys=ok[:no], odepth=od[:no], olabel=ol[:no],
+                    ns=a.value, no=b.value)
+
+    def object_groups(self, cur_keys, cur_depth, cur_label, last_keys, last_depth, last_label,
+                      Tcur, Tlast, K, W, H):
+        """B6 + B7 statistics: dict(obj_label n, members: list of 16 index arrays, cnt, bcnt,
+        sfcnt, n_members 16 ints, depth_sum 16 floats, hist 16 x 16, err).  A label above 15
+        raises MmtError."""
+        ck = np.ascontiguousarray(cur_keys, np.float32).reshape(-1, 2)
+        lk = np.ascontiguousarray(last_keys, np.float32).reshape(-1, 2)
+        cd = np.ascontiguousarray(cur_depth, np.float32)
+        ld = np.ascontiguousarray(last_depth, np.float32)
+        cl = np.ascontiguousarray(cur_label, np.int32)
+        ll = np.ascontiguousarray(last_label, np.int32)
+        n = len(cd)
+        assert len(ck) == len(lk) == len(ld) == len(cl) == len(ll) == n
+        pr = MmtObjGroupProblem()
+        pr.n = n
+        pr.cur_keys, pr.cur_depth, pr.cur_label = ck.ctypes.data, cd.ctypes.data, cl.ctypes.data
+        pr.last_keys, pr.last_depth, pr.last_label = lk.ctypes.data, ld.ctypes.data, ll.ctypes.data
+        pr.Tcur[:] = np.asarray(Tcur, np.float32).reshape(16).tolist()
+        pr.Tlast[:] = np.asarray(Tlast, np.float32).reshape(16).tolist()
+        pr.fx, pr.fy, pr.cx, pr.cy = K
+        pr.W, pr.H = W, H
+        m = max(n, 1)
+        ol = np.zeros(m, np.int32)
+        mem = np.zeros((16, m), np.int32)
+        st = np.zeros((16, 8), np.int32)
+        hist = np.zeros((16, 16), np.int32)
+        err = ctypes.c_int(0)
+        self._check(lib().mmt_object_groups(self._h, ctypes.byref(pr), _p(ol), _p(mem), _p(st),
+                                            _p(hist), ctypes.byref(err)))
+        nm = st[:, 3].copy()
+        return dict(obj_label=ol[:n], members=[mem[l, :max(int(nm[l]), 0)].copy() for l in range(16)],
+                    members_raw=mem[:, :n], cnt=st[:, 0].copy(), bcnt=st[:, 1].copy(),
+                    sfcnt=st[:, 2].copy(), n_members=nm,
+                    depth_sum=st[:, 4].copy().view(np.float32), hist=hist, err=err.value)
 
     # ---- B3 / C1-C3 probes (Frame grid, ORBmatcher::SearchByProjection) -------------------
     @staticmethod

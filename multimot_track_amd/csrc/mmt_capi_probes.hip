@@ -170,6 +170,31 @@ static void check_sft_keyframe(const mmt_sft_keyframe* k) {
   check_feature_vector(&k->fv, k->n, &once, INT32_MAX);
 }
 
+// An output array of a sample-set probe: `cap` elements the kernel may write and a guard behind
+// them, all bytes 0xFF before the launch.  down() copies the cap elements out (entries the kernel
+// left alone keep the fill) and throws when the guard changed: a write past the capacity.
+template <typename T>
+struct GuardedOut {
+  static constexpr size_t kGuard = 16;
+  DevBuf<T> b;
+  size_t cap;
+  GuardedOut(size_t cap_, hipStream_t s) : b(cap_ + kGuard), cap(cap_) {
+    MMT_HIP(hipMemsetAsync(b.p, 0xFF, (cap + kGuard) * sizeof(T), s));
+  }
+  void down(T* h, hipStream_t s) const {
+    uint8_t g[kGuard * sizeof(T)];
+    b.down(h, cap, s);
+    MMT_HIP(hipMemcpyAsync(g, b.p + cap, sizeof(g), hipMemcpyDeviceToHost, s));
+    MMT_HIP(hipStreamSynchronize(s));
+    for (uint8_t x : g)
+      if (x != 0xFF) throw DeviceError("object front end probe: write past the output capacity");
+  }
+};
+
+static void check_image(int W, int H) {
+  if (W <= 0 || H <= 0 || (int64_t)W * H > (int64_t)1 << 26) throw ArgError("bad image size");
+}
+
 extern "C" {
 
 // init_on_device: the initial pose goes to device memory and the descriptor names it (init_dev),
@@ -961,6 +986,211 @@ int mmt_pnpsolver_iterate(mmt_ctx* ctx, const mmt_pnpsolver_problem* pr, const i
     MMT_HIP(hipSetDevice(ctx->cfg.device_id));
     mmt::pnpsolver_iterate_gpu(ctx->stream, pr, randi, n_draw_iters, n_iterations, st, Tcw_out,
                                inliers_out, n_inliers, pose_found, no_more);
+  });
+}
+
+// ---- object front end probes (A2, B1, B2, B4, B6 + B7 statistics)
+int mmt_gray_depth(mmt_ctx* ctx, const uint8_t* bgr, size_t bgr_pitch, const uint16_t* disp,
+                   size_t disp_pitch, int npix, int nframes, float bf, uint8_t* gray,
+                   size_t gray_pitch, float* depth, size_t depth_pitch) {
+  if (!ctx || !bgr || !disp || !gray || !depth) return MMT_EINVAL;
+  return guard(ctx, [&] {
+    if (npix <= 0 || npix > 1 << 26 || nframes <= 0 || nframes > 64)
+      throw ArgError("bad pixel or frame count");
+    if (bgr_pitch < 3 * (size_t)npix || disp_pitch < (size_t)npix || gray_pitch < (size_t)npix ||
+        depth_pitch < (size_t)npix)
+      throw ArgError("frame pitch below the frame size");
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const size_t nf = (size_t)nframes;
+    DevBuf<uint8_t> B(nf * bgr_pitch), G(nf * gray_pitch);
+    DevBuf<uint16_t> D(nf * disp_pitch);
+    DevBuf<float> Z(nf * depth_pitch);
+    B.up(bgr, nf * bgr_pitch, s);
+    D.up(disp, nf * disp_pitch, s);
+    G.up(gray, nf * gray_pitch, s);  // the outputs' padding keeps the caller's bytes
+    Z.up(depth, nf * depth_pitch, s);
+    mmt::launch_gray_depth(B.p, bgr_pitch, D.p, disp_pitch, G.p, gray_pitch, Z.p, depth_pitch,
+                           npix, nframes, bf, s);
+    G.down(gray, nf * gray_pitch, s);
+    Z.down(depth, nf * depth_pitch, s);
+    MMT_HIP(hipStreamSynchronize(s));
+  });
+}
+
+int mmt_static_samples(mmt_ctx* ctx, const mmt_kp* kps, int n, const float* depth,
+                       const float* flow, const int32_t* mask, int W, int H, int cap,
+                       float* keys_out, float* corres_out, float* flow_out, float* depth_out,
+                       int* count) {
+  if (!ctx || !depth || !flow || !mask || !keys_out || !corres_out || !flow_out || !depth_out ||
+      !count || n < 0 || (n > 0 && !kps) || cap < 0)
+    return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_image(W, H);
+    for (int i = 0; i < n; i++)  // the kernel reads the maps at the truncated key, unchecked
+      if (!(kps[i].x >= 0 && kps[i].y >= 0 && (int)kps[i].x < W && (int)kps[i].y < H))
+        throw ArgError("keypoint outside the image");
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const size_t np = (size_t)W * H;
+    DevBuf<mmt_kp> K(n);
+    DevBuf<int> nk(1), cnt(1);
+    DevBuf<float> Z(np);
+    DevBuf<float2> F(np);
+    DevBuf<int32_t> M(np);
+    GuardedOut<float2> ok(cap, s), oc(cap, s), of(cap, s);
+    GuardedOut<float> od(cap, s);
+    K.up(kps, n, s);
+    nk.up(&n, 1, s);
+    Z.up(depth, np, s);
+    F.up((const float2*)flow, np, s);
+    M.up(mask, np, s);
+    mmt::SampleSet out{ok.b.p, oc.b.p, of.b.p, od.b.p, cnt.p, cap};
+    mmt::launch_static_samples(K.p, nk.p, Z.p, F.p, M.p, W, H, out, s);
+    cnt.down(count, 1, s);
+    ok.down((float2*)keys_out, s);
+    oc.down((float2*)corres_out, s);
+    of.down((float2*)flow_out, s);
+    od.down(depth_out, s);
+  });
+}
+
+int mmt_object_samples(mmt_ctx* ctx, const float* depth, const float* flow, const int32_t* mask,
+                       int W, int H, int cap, float* keys_out, float* corres_out, float* flow_out,
+                       float* depth_out, int32_t* label_out, int* count) {
+  if (!ctx || !depth || !flow || !mask || !keys_out || !corres_out || !flow_out || !depth_out ||
+      !label_out || !count || cap < 0)
+    return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_image(W, H);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const size_t np = (size_t)W * H;
+    DevBuf<int> cnt(1), blocks(64);
+    DevBuf<float> Z(np);
+    DevBuf<float2> F(np);
+    DevBuf<int32_t> M(np);
+    GuardedOut<float2> ok(cap, s), oc(cap, s), of(cap, s);
+    GuardedOut<float> od(cap, s);
+    GuardedOut<int32_t> ol(cap, s);
+    Z.up(depth, np, s);
+    F.up((const float2*)flow, np, s);
+    M.up(mask, np, s);
+    mmt::ObjSampleSet out{ok.b.p, oc.b.p, of.b.p, od.b.p, ol.b.p, cnt.p, cap, blocks.p};
+    mmt::launch_obj_samples(Z.p, F.p, M.p, W, H, out, s);
+    cnt.down(count, 1, s);
+    ok.down((float2*)keys_out, s);
+    oc.down((float2*)corres_out, s);
+    of.down((float2*)flow_out, s);
+    od.down(depth_out, s);
+    ol.down(label_out, s);
+  });
+}
+
+int mmt_sample_handoff(mmt_ctx* ctx, const float* last_corres, int ns, const float* last_obj_corres,
+                       int no, const float* depth, const int32_t* mask, int W, int H,
+                       float* skeys_out, float* sdepth_out, float* okeys_out, float* odepth_out,
+                       int32_t* olabel_out, int* ns_out, int* no_out) {
+  if (!ctx || !depth || !mask || !ns_out || !no_out || ns < 0 || no < 0 ||
+      (ns > 0 && (!last_corres || !skeys_out || !sdepth_out)) ||
+      (no > 0 && (!last_obj_corres || !okeys_out || !odepth_out || !olabel_out)))
+    return MMT_EINVAL;
+  return guard(ctx, [&] {
+    check_image(W, H);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const size_t np = (size_t)W * H;
+    DevBuf<float2> lc(ns), loc(no);
+    DevBuf<int> dn(4);
+    DevBuf<float> Z(np);
+    DevBuf<int32_t> M(np);
+    GuardedOut<float2> sk(ns, s), okk(no, s);
+    GuardedOut<float> sd(ns, s), od(no, s);
+    GuardedOut<int32_t> ol(no, s);
+    const int hn[4] = {ns, no, -1, -1};
+    lc.up((const float2*)last_corres, ns, s);
+    loc.up((const float2*)last_obj_corres, no, s);
+    dn.up(hn, 4, s);
+    Z.up(depth, np, s);
+    M.up(mask, np, s);
+    mmt::HandoffSet cur{sk.b.p, sd.b.p, dn.p + 2, okk.b.p, od.b.p, ol.b.p, dn.p + 3};
+    mmt::launch_handoff(lc.p, dn.p, loc.p, dn.p + 1, Z.p, M.p, W, H, cur, s);
+    int back[4];
+    dn.down(back, 4, s);
+    if (ns > 0) {
+      sk.down((float2*)skeys_out, s);
+      sd.down(sdepth_out, s);
+    }
+    if (no > 0) {
+      okk.down((float2*)okeys_out, s);
+      od.down(odepth_out, s);
+      ol.down(olabel_out, s);
+    }
+    MMT_HIP(hipStreamSynchronize(s));
+    *ns_out = back[2];
+    *no_out = back[3];
+  });
+}
+
+int mmt_object_groups(mmt_ctx* ctx, const mmt_obj_group_problem* pr, int32_t* obj_label_out,
+                      int32_t* members_out, int32_t* stats_out, int32_t* hist_out, int* err_out) {
+  if (!ctx || !pr || !stats_out || !hist_out || !err_out || pr->n < 0 ||
+      (pr->n > 0 && (!pr->cur_keys || !pr->cur_depth || !pr->cur_label || !pr->last_keys ||
+                     !pr->last_depth || !pr->last_label || !obj_label_out || !members_out)))
+    return MMT_EINVAL;
+  static_assert(sizeof(mmt::LabelStats) == 32, "stats_out is 8 words per label");
+  return guard(ctx, [&] {
+    check_image(pr->W, pr->H);
+    MMT_HIP(hipSetDevice(ctx->cfg.device_id));
+    hipStream_t s = ctx->stream;
+    const int n = pr->n, mcap = std::max(n, 1);  // member_cap = n, as the tracker's ocap_ >= n
+    DevBuf<float2> ck(n), lk(n);
+    DevBuf<float> cd(n), ld(n);
+    DevBuf<int32_t> cl(n), ll(n);
+    DevBuf<int> dn(1), err(1), hist(mmt::kMaxLabel * mmt::kMaxLabel);
+    DevBuf<mmt::LabelStats> stats(mmt::kMaxLabel);
+    GuardedOut<int32_t> ol(n, s);
+    GuardedOut<int> mem((size_t)mmt::kMaxLabel * mcap, s);
+    ck.up((const float2*)pr->cur_keys, n, s);
+    cd.up(pr->cur_depth, n, s);
+    cl.up(pr->cur_label, n, s);
+    lk.up((const float2*)pr->last_keys, n, s);
+    ld.up(pr->last_depth, n, s);
+    ll.up(pr->last_label, n, s);
+    dn.up(&n, 1, s);
+    MMT_HIP(hipMemsetAsync(err.p, 0, sizeof(int), s));
+    MMT_HIP(hipMemsetAsync(stats.p, 0xFF, sizeof(mmt::LabelStats) * mmt::kMaxLabel, s));
+    mmt::GroupArgs g;
+    memset(&g, 0, sizeof(g));
+    g.n = dn.p;
+    g.cur_keys = ck.p;
+    g.cur_depth = cd.p;
+    g.cur_label = cl.p;
+    g.last_keys = lk.p;
+    g.last_depth = ld.p;
+    g.last_label = ll.p;
+    memcpy(g.Tcur, pr->Tcur, sizeof(g.Tcur));
+    memcpy(g.Tlast, pr->Tlast, sizeof(g.Tlast));
+    g.fx = pr->fx; g.fy = pr->fy; g.cx = pr->cx; g.cy = pr->cy;
+    g.W = pr->W;
+    g.H = pr->H;
+    g.obj_label = ol.b.p;
+    g.members = mem.b.p;
+    g.member_cap = mcap;
+    g.stats = stats.p;
+    g.hist = hist.p;
+    g.err = err.p;
+    mmt::launch_obj_group(g, s);
+    err.down(err_out, 1, s);
+    stats.down((mmt::LabelStats*)stats_out, mmt::kMaxLabel, s);
+    hist.down(hist_out, mmt::kMaxLabel * mmt::kMaxLabel, s);
+    if (n > 0) {
+      ol.down(obj_label_out, s);
+      mem.down(members_out, s);
+    }
+    MMT_HIP(hipStreamSynchronize(s));
+    // the flag lives in this call's own buffer: the next call starts clean
+    if (*err_out) throw ArgError("semantic label outside [0, 15] on the object path");
   });
 }
 

@@ -5,10 +5,9 @@
 #include <cstdint>
 
 #include "../../include/mmt.h"
+#include "mmt_objdecide.h"
 
 namespace mmt {
-
-constexpr int kMaxLabel = 16;  // semantic labels 0..15 per frame (LoadMask keeps 1..3)
 
 // Static samples of one frame: mvSiftKeysTmp / mvCorres / mvFlowNext / mvSiftDepthTmp.
 struct SampleSet {
@@ -41,12 +40,6 @@ struct HandoffSet {
   float* odepth;
   int32_t* olabel;
   int* no;
-};
-
-struct LabelStats {
-  int cnt, bcnt, sfcnt, members;
-  float depth_sum;
-  int pad[3];
 };
 
 struct GroupArgs {

@@ -897,53 +897,12 @@ void Tracker::obj_stage_a_decide(ObjFrame& F) {
   }
   const LabelStats* stats = H.stats;
   const int* hist = H.hist;
-  // ---- B7 decisions (Tracking.cc:1424-1536); labels ascending = UniLab order
-  std::vector<int> objLabelsNew;  // semantic label of each kept object
-  for (int l = 1; l < kMaxLabel; l++) {
-    const LabelStats& s = stats[l];
-    if (s.cnt == 0) continue;
-    const float count = (float)s.bcnt;
-    if (count / s.cnt > 0.5f) continue;  // mostly on the image boundary
-    if (!(s.cnt > 100)) continue;        // fewer than 100 points
-    const float sf_count = (float)s.sfcnt;
-    if (sf_count / s.cnt > 0.3f) continue;            // static object
-    if (s.depth_sum / s.cnt > 25.0) continue;         // too far
-    objLabelsNew.push_back(l);
-  }
-  // ---- B8 label association (Tracking.cc:1556-1630)
-  int mx;
-  if (C.bSecond)
-    mx = 1;
-  else if (!Ls.nModLabel.empty())
-    mx = *std::max_element(Ls.nModLabel.begin(), Ls.nModLabel.end()) + 1;
-  else
-    mx = 1;  // uninitialised in the reference (Tracking.cc:1557): pinned 1
+  // ---- B7 decisions and B8 label association (mmt_objdecide.cpp)
+  const ObjDecision dec = obj_decide(stats, hist, C.bSecond, Ls.nModLabel, Ls.nSemPosition);
+  const std::vector<int>& objLabelsNew = dec.labels;  // semantic label of each kept object
+  const std::vector<int>& LabId = dec.LabId;
   const int nobj = (int)objLabelsNew.size();
   if (nobj > kMaxObj) throw ArgError("more dynamic objects than semantic labels 1..15");
-  std::vector<int> LabId(nobj);
-  for (int i = 0; i < nobj; i++) {
-    const int l = objLabelsNew[i];
-    int New_lab = 0, best = -1;
-    for (int ll = 0; ll < kMaxLabel; ll++) {  // std::map order: ascending last label
-      const int c = hist[l * kMaxLabel + ll];
-      if (c > best && c > 0) {
-        best = c;
-        New_lab = ll;
-      }
-    }
-    if (C.bSecond) {
-      LabId[i] = mx++;
-    } else {
-      bool exist = false;
-      for (size_t k = 0; k < Ls.nSemPosition.size(); k++)
-        if (Ls.nSemPosition[k] == New_lab) {
-          LabId[i] = Ls.nModLabel[k];
-          exist = true;
-          break;
-        }
-      if (!exist) LabId[i] = mx++;
-    }
-  }
   C.nModLabel = LabId;
   C.nSemPosition.assign(objLabelsNew.begin(), objLabelsNew.begin() + nobj);
   C.vObjMod.assign(nobj, std::vector<float>(16, 0.f));
