@@ -259,7 +259,7 @@ void MapEngine::map_point_culling(int kf) {  // LocalMapping::MapPointCulling (R
 }
 
 // ------------------------------------------------------------------ GPU stages
-// D1's descriptor for an edge list that k_map_edges builds on the device (it writes n): the edge
+// D1's descriptor for an edge list that k_match_fix builds on the device (it writes n): the edge
 // arrays at a fixed capacity of kcap edges
 void MapEngine::pose_desc_fill(uint8_t* h_blk, uint8_t* d_blk, const float* Tcw) {
   h_pod_ = (PoseOptDesc*)h_blk;

@@ -98,7 +98,7 @@ struct LastFrameDev {
 struct MapEdgeArgs;
 // run_if (optional): the call runs only while *run_if < run_lt (C2's retry at a wider window when
 // the first search found too few matches), decided on the device.  edges (optional): the matcher
-// kernel also builds D1's edge list from its final bindings (k_map_edges' work, no launch of its
+// kernel also builds D1's edge list from its final bindings (map_edges_body, no launch of its
 // own); a call that does not run leaves the previous call's list.
 void launch_sbp_frame(const GridFrame& C, const float* Tcw, const LastFrameDev& L, float th,
                       int mono, int check_orientation, const CandSet& cs, int* match,
@@ -201,7 +201,6 @@ struct MapEdgeArgs {
   float* s2;
   PoseOptDesc* desc;
 };
-void launch_map_edges(const MapEdgeArgs& a, hipStream_t st);
 
 // pool maintenance: scatter n packed (handle, record, descriptor) updates into the pool
 struct alignas(16) PoolUpdate {

@@ -32,6 +32,7 @@
 #include "mmt_internal.h"
 #include "mmt_match.h"
 #include "mmt_track.h"
+#include "mmt_wgscan.h"
 
 namespace mmt {
 
@@ -40,27 +41,6 @@ static constexpr int HISTO_LENGTH = 30;  // ORBmatcher.cc:43
 static constexpr uint32_t kNoCand = 0xFFFFFFFFu;
 
 // ------------------------------------------------------------------------------ helpers
-__device__ __forceinline__ int grid_block_scan_excl(int v, int* s_w, int& excl) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_w[wave] = x;
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < nw; w++) {
-    const int c = s_w[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  excl = off + x - v;
-  __syncthreads();
-  return tot;
-}
-
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
@@ -159,7 +139,7 @@ __global__ __launch_bounds__(1024) void k_stereo_grid(const mmt_kp* __restrict__
   // exclusive scan over the 3072 cells, three per thread (blockDim == 1024)
   const int a0 = s_cnt[3 * t], a1 = s_cnt[3 * t + 1], a2 = s_cnt[3 * t + 2];
   int excl = 0;
-  const int tot = grid_block_scan_excl(a0 + a1 + a2, s_w, excl);
+  const int tot = block_scan_excl(a0 + a1 + a2, s_w, excl);
   s_cnt[3 * t] = excl;
   s_cnt[3 * t + 1] = excl + a0;
   s_cnt[3 * t + 2] = excl + a0 + a1;
@@ -644,7 +624,7 @@ struct OwnerTaken {
 // may need a rescan).  Rounds then read LDS only.
 constexpr uint32_t kPackNone = 0xFFFFFFFFu;
 
-// D1's edge list in key order (k_map_edges; also the tail of k_match_fix): a key with a new match
+// D1's edge list in key order (the tail of k_match_fix): a key with a new match
 // takes its point's position, a key bound before the search its held position; nothing is built
 // below min_matches (build false).  One 1024-thread workgroup; writes desc->n.
 __device__ __forceinline__ void map_edges_body(const MapEdgeArgs& a, bool build, int* s_w) {
@@ -660,7 +640,7 @@ __device__ __forceinline__ void map_edges_body(const MapEdgeArgs& a, bool build,
         src = 1;
     }
     int excl = 0;
-    const int tot = grid_block_scan_excl(src >= 0 ? 1 : 0, s_w, excl);
+    const int tot = block_scan_excl(src >= 0 ? 1 : 0, s_w, excl);
     if (src >= 0) {
       const int e = base + excl;
       const float* X;
@@ -1594,18 +1574,6 @@ void launch_search_by_bow_keyframes(const BowKfArgs& a, hipStream_t st) {
     MMT_HIP(hipGetLastError());
   }
   hipLaunchKernelGGL(k_bow_kf_rot, dim3(a.n_cand), dim3(256), 0, st, a);
-  MMT_HIP(hipGetLastError());
-}
-
-// ------------------------------------------------------------------------------ D1 edges
-// One 1024-thread workgroup: order-preserving compaction of the bound keys, 1024 keys per step.
-__global__ __launch_bounds__(1024) void k_map_edges(MapEdgeArgs a) {
-  __shared__ int s_w[16];
-  map_edges_body(a, !a.nm || *a.nm >= a.min_matches, s_w);
-}
-
-void launch_map_edges(const MapEdgeArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_map_edges, dim3(1), dim3(1024), 0, st, a);
   MMT_HIP(hipGetLastError());
 }
 

@@ -48,11 +48,8 @@ struct PnPObject {
 constexpr int kHypRec = 160;  // doubles per hypothesis record
 constexpr int kHypOut = 16;   // doubles per (hypothesis, beta variant) result
 
-// RANSAC + refit (everything but the motion-model check)
+// RANSAC + refit (the motion-model check is k_obj_stage_b's, mmt_tracker.hip)
 void launch_pnp(PnPObject* d_objs, int nobj, int max_iters, hipStream_t st, bool gather = true);
-// motion-model inliers (needs PnPObject::MM, i.e. the previous frame's object motions)
-void launch_pnp_mm(PnPObject* d_objs, int nobj, hipStream_t st);
-void launch_pnp_subset(PnPObject* d_objs, int nobj, hipStream_t st);
 // D6: P4P hypotheses (subsets [K][4]), their chosen estimates (hrt) and CheckInliers (good,
 // masks rows 0..K-1)
 void launch_p4p_hypotheses(PnPObject* d_obj, int K, hipStream_t st);
@@ -65,56 +62,5 @@ void pnpsolver_iterate_gpu(hipStream_t s, const mmt_pnpsolver_problem* pr, const
                            int n_draw_iters, int n_iterations, mmt_pnpsolver_state* st,
                            float* Tcw_out, uint8_t* inliers_out, int* n_inliers, int* pose_found,
                            int* no_more);
-
-
-#ifdef __HIPCC__
-// motion-model inliers, ascending (GetInitModelObj, Tracking.cc:4380-4399); MM row-major float.
-// Block-level (256 threads, every thread of the workgroup calls it).
-__device__ inline void pnp_mm_inliers_block(PnPObject& o) {
-  __shared__ int s_w[4];
-  if (!o.use_mm) return;
-  const int n = *o.n;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += blockDim.x) {
-    const int i = i0 + threadIdx.x;
-    bool in = false;
-    if (i < n) {
-      float xc[3];
-      for (int r = 0; r < 3; r++) {
-        double s = 0;
-        for (int k = 0; k < 3; k++) s += (double)o.MM[4 * r + k] * (double)o.pts3[3 * i + k];
-        xc[r] = (float)s + o.MM[4 * r + 3];
-      }
-      const float invzc = (float)(1.0 / (double)xc[2]);
-      const float u = o.fx * xc[0] * invzc + o.cx, v = o.fy * xc[1] * invzc + o.cy;
-      const float2 q = o.pts2[i];
-      const float u_ = q.x - u, v_ = q.y - v;
-      const float Rpe = sqrtf(u_ * u_ + v_ * v_);
-      in = (double)Rpe < o.reproj;
-    }
-    const unsigned long long bal = __ballot(in);
-    if (lane == 0) s_w[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < 4; w++) {
-      if (w < wave) off += s_w[w];
-      tot += s_w[w];
-    }
-    if (in) o.mm_inliers[base + off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-    base += tot;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) o.result[4] = base;
-}
-
-// D3 edge index list: ObjId_sub[i] = ObjId[inliers[i]] (sample indices) of the chosen model
-__device__ inline void pnp_subset_block(PnPObject& o) {
-  const int n = o.use_mm_choice ? o.result[4] : o.result[3];
-  const int* src = o.use_mm_choice ? o.mm_inliers : o.inliers;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) o.subset[i] = o.members[src[i]];
-  if (threadIdx.x == 0) *o.n_subset = n;
-}
-#endif
 
 }  // namespace mmt

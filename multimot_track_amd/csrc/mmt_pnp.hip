@@ -1,22 +1,28 @@
-// multimot_track_amd/csrc/mmt_pnp.hip -- object-motion initialiser D5 on the GPU:
-// cv::solvePnPRansac(pre_3d, cur_2d, K, 0, ..., 500, 0.3, 0.98, inliers, SOLVEPNP_AP3P) as
-// called by Tracking::GetInitModelObj (reference src/Tracking.cc:4324-4443).
+// multimot_track_amd/csrc/mmt_pnp.hip -- the two EPnP-RANSAC solvers on the GPU.
+// D5, the object-motion initialiser: cv::solvePnPRansac(pre_3d, cur_2d, K, 0, ..., 500, 0.3,
+// 0.98, inliers, SOLVEPNP_AP3P) as called by Tracking::GetInitModelObj (reference
+// src/Tracking.cc:4324-4443).  D6, relocalisation: PnPsolver::iterate (PnPsolver.cc:119-264).
 //
-//   k_pnp_gather   pre_3d = UnprojectStereoObject(last sample), cur_2d = current sample
-//   k_pnp_hyp      one wave per RANSAC hypothesis: 5-point EPnP (PnPsolver.cc:342-1022 lineage)
-//                  on the subset drawn by RNG((uint64)-1) (precomputed on the host: the draw
-//                  sequence depends only on the point count) up to the null space of M^T M
-//   k_pnp_beta<V>  one lane per hypothesis: beta estimate V, Gauss-Newton, R and t
-//   k_pnp_score    picks the best estimate (Rodrigues -> model), then one workgroup per
-//                  hypothesis scores it
-//                  (projectPoints + squared-error test, inlier count by ballot/popcount,
-//                  inlier bit mask)
-//   k_pnp_select   replay of RANSACPointSetRegistrator::run's best-so-far / niters logic
-//   k_refit_*      EPnP over all RANSAC inliers (reductions over the points, block-wide 12x12
-//                  eigen-solve, beta estimates in lanes, one Procrustes solve per wave)
-//   k_mm_inliers   motion-model check (Tracking.cc:4375-4405)
-// The dense algebra (cyclic/one-sided Jacobi) follows oracle/pnp_ref.cpp operation for
-// operation so hypothesis models agree to the last bit with the CPU checker.
+//   k_pnp_gather      D5: pre_3d = UnprojectStereoObject(last sample), cur_2d = current sample
+//   k_pnp_hyp<NP>     12 lanes per RANSAC hypothesis, five per wave: EPnP (PnPsolver.cc:342-1022
+//                     lineage) on a minimal set up to the null space of M^T M, L_6x10 and rho.
+//                     NP = 5: D5's sets, drawn by RNG((uint64)-1) (precomputed on the host: the
+//                     draw sequence depends only on the point count); NP = 4: D6's P4P sets
+//   k_pnp_beta<NP>    one lane per (hypothesis, beta estimate): Gauss-Newton, R, t and the
+//                     reprojection error
+//   k_pnp_score       D5, one workgroup per hypothesis: the chosen estimate (Rodrigues ->
+//                     model), then projectPoints + squared-error test, inlier mask and count
+//   k_pnp_select      D5: replay of RANSACPointSetRegistrator::run's best-so-far / niters logic
+//   k_refit_null      EPnP over the inliers of a mask row, one workgroup per object: inlier list,
+//                     control points, M^T M (workgroup sums), 12x12 eigen-solve, L_6x10, rho
+//   k_refit_beta      the three beta estimates -> control points in the camera frame
+//   k_refit_rt        R, t and reprojection error of the three estimates, the best one's pose
+//   k_p4p_check       D6, one workgroup per hypothesis: the chosen estimate, then CheckInliers
+//   k_p4p_check_rt    D6: CheckInliers of the refined pose
+//   k_p4p_set_row     D6: the mask row the refit reads
+// Every stage of EPnP is stated once (epnp_*, best_of_three) and called by the hypothesis and
+// the refit kernels.  The dense algebra (cyclic/one-sided Jacobi) follows oracle/pnp_ref.cpp
+// operation for operation so hypothesis models agree to the last bit with the CPU checker.
 
 #include <hip/hip_runtime.h>
 
@@ -30,6 +36,7 @@
 #include "mmt_internal.h"
 #include "mmt_devmath.h"
 #include "mmt_pnp.h"
+#include "mmt_wgscan.h"
 
 namespace mmt {
 
@@ -394,17 +401,120 @@ __device__ __forceinline__ void gauss_newton(const double (&L)[60], const double
   }
 }
 
-// ccs = sum_i betas[i] * ut row (11 - i)  (compute_ccs)
-__device__ __forceinline__ void compute_ccs(const double* ut, const double (&betas)[4],
-                                            double (&ccs)[12]) {
+// ---------------------------------------------------------------- the stages of EPnP
+// Pure arithmetic on the values handed in, shared by the hypothesis kernels (a minimal set per
+// lane, points in registers) and the refit kernels (all inliers, workgroup sums): how the points
+// are walked and summed stays with each kernel.
+//
+// EPnP record layout (doubles): the four null-space vectors ut rows 8..11, alphas, pws, us,
+// L_6x10, rho.  A hypothesis fills all of it; the refit keeps cws in R_AL and ci in R_PW.
+constexpr int R_UT = 0, R_AL = 48, R_PW = 68, R_US = 83, R_L = 93, R_RHO = 153;
+
+// choose_control_points + the pseudo-inverse of compute_barycentric_coordinates: cws[0..2] holds
+// the centroid of the `count` points on entry, m their second moments about it (destroyed)
+__device__ __forceinline__ void epnp_control_points(double (&cws)[12], double (&m)[9], int count,
+                                                    double (&ci)[9]) {
+  double dc[3], uct[9], cc[9];
+  eig_sym_small<3>(m, dc, uct);
+#pragma unroll
+  for (int i = 1; i < 4; i++) {
+    const double k = sqrt(fmax(dc[i - 1], 0.0) / count);
+#pragma unroll
+    for (int x = 0; x < 3; x++) cws[3 * i + x] = cws[x] + k * uct[3 * (i - 1) + x];
+  }
+#pragma unroll
+  for (int i = 0; i < 3; i++)
+#pragma unroll
+    for (int x = 1; x < 4; x++) cc[3 * i + x - 1] = cws[3 * x + i] - cws[i];
+  pinv3(cc, ci);
+}
+
+// barycentric coordinates of the world point p
+__device__ __forceinline__ void epnp_alphas(const double* p, const double* cws, const double* ci,
+                                            double* al) {
+#pragma unroll
+  for (int x = 0; x < 3; x++)
+    al[1 + x] = ci[3 * x] * (p[0] - cws[0]) + ci[3 * x + 1] * (p[1] - cws[1]) +
+                ci[3 * x + 2] * (p[2] - cws[2]);
+  al[0] = 1.0f - al[1] - al[2] - al[3];
+}
+
+// L_6x10 and rho into the record, from the null-space vectors and the control points
+__device__ __forceinline__ void epnp_L_rho(const double* ut8, const double* cws, double* rec) {
+  double L[60];
+  compute_L_6x10(ut8, L);
+#pragma unroll
+  for (int i = 0; i < 60; i++) rec[R_L + i] = L[i];
+  rec[R_RHO + 0] = d_dist2(cws + 0, cws + 3);
+  rec[R_RHO + 1] = d_dist2(cws + 0, cws + 6);
+  rec[R_RHO + 2] = d_dist2(cws + 0, cws + 9);
+  rec[R_RHO + 3] = d_dist2(cws + 3, cws + 6);
+  rec[R_RHO + 4] = d_dist2(cws + 3, cws + 9);
+  rec[R_RHO + 5] = d_dist2(cws + 6, cws + 9);
+}
+
+// beta estimate V, Gauss-Newton, then compute_ccs: ccs = sum_i betas[i] * ut row (11 - i)
+template <int V>
+__device__ __forceinline__ void epnp_ccs(const double* rec, double (&ccs)[12]) {
+  double L[60], rho[6], betas[4];
+#pragma unroll
+  for (int i = 0; i < 60; i++) L[i] = rec[R_L + i];
+#pragma unroll
+  for (int i = 0; i < 6; i++) rho[i] = rec[R_RHO + i];
+  if (V == 1)
+    betas_approx_1(L, rho, betas);
+  else if (V == 2)
+    betas_approx_2(L, rho, betas);
+  else
+    betas_approx_3(L, rho, betas);
+  gauss_newton(L, rho, betas);
 #pragma unroll
   for (int i = 0; i < 12; i++) ccs[i] = 0.0f;
 #pragma unroll
   for (int i = 0; i < 4; i++) {
-    const double* v = ut + 12 * (11 - i);
+    const double* v = rec + R_UT + 12 * (3 - i);  // ut row 11 - i
 #pragma unroll
     for (int j = 0; j < 12; j++) ccs[j] += betas[i] * v[j];
   }
+}
+
+// camera-frame point (compute_pcs) from its alphas and the camera-frame control points
+__device__ __forceinline__ void epnp_pc(const double* al, const double* ccs, double* pc) {
+#pragma unroll
+  for (int j = 0; j < 3; j++)
+    pc[j] = al[0] * ccs[j] + al[1] * ccs[3 + j] + al[2] * ccs[6 + j] + al[3] * ccs[9 + j];
+}
+
+// solve_for_sign's test: the first point (alphas al0) lies behind the camera, so ccs and every
+// camera-frame point computed from it change sign
+__device__ __forceinline__ bool epnp_behind_camera(const double* al0, const double* ccs) {
+  double pc[3];
+  epnp_pc(al0, ccs, pc);
+  return pc[2] < 0.0;
+}
+
+// estimate_R_and_t from the cross-covariance abt (destroyed) and the two centroids
+__device__ __forceinline__ void epnp_R_t(double (&abt)[9], const double* pc0, const double* pw0,
+                                         double (&R)[9], double* t) {
+  procrustes_R(abt, R);
+#pragma unroll
+  for (int r = 0; r < 3; r++) t[r] = pc0[r] - d_dot3(R + 3 * r, pw0);
+}
+
+// one point's term of reprojection_error: pixel distance of pw under (R, t) from (u, v)
+__device__ __forceinline__ double epnp_reproj_dist(const double* R, const double* t,
+                                                   const double* pw, double u, double v, double fu,
+                                                   double fv, double uc, double vc) {
+  const double Xc = d_dot3(R, pw) + t[0], Yc = d_dot3(R + 3, pw) + t[1];
+  const double inv_Zc = 1.0 / (d_dot3(R + 6, pw) + t[2]);
+  const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
+  return sqrt((u - ue) * (u - ue) + (v - ve) * (v - ve));
+}
+
+// compute_pose's choice among the three beta estimates (rep_errors[2] < [1]; [3] < [N])
+__device__ __forceinline__ int best_of_three(double e0, double e1, double e2) {
+  const int best = e1 < e0 ? 1 : 0;
+  return e2 < (best ? e1 : e0) ? 2 : best;
 }
 
 __device__ void d_rodrigues_r2v(const double R[9], double r[3]) {
@@ -470,7 +580,6 @@ __device__ __forceinline__ void rr_partner(int r, int j, int& p, int& q) {
 
 __device__ __forceinline__ int eig12_group(double (&a)[12], double (&v)[12], int gb, int j,
                                            bool active, int& rank) {
-  const int lane = threadIdx.x & 63;
   const unsigned long long gmask = active ? (0xFFFull << gb) : 0ull;
   int sweep = 0;
   for (; sweep < 100; sweep++) {
@@ -525,7 +634,6 @@ __device__ __forceinline__ int eig12_group(double (&a)[12], double (&v)[12], int
     const double si = __shfl(sig, gb + i, 64);
     rank += (si > sig) || (i < j && si == sig);
   }
-  (void)lane;
   return sweep;
 }
 
@@ -552,10 +660,6 @@ __global__ __launch_bounds__(256) void k_pnp_gather(PnPObject* objs) {
     o.pts2[i] = o.cur_keys[s];
   }
 }
-
-// Hypothesis record layout (doubles): the four null-space vectors ut rows 8..11, alphas, pws,
-// us, L_6x10, rho
-constexpr int R_UT = 0, R_AL = 48, R_PW = 68, R_US = 83, R_L = 93, R_RHO = 153;
 
 // 64-lane workgroup = five hypotheses (lanes 12g..12g+11 for hypothesis g): 5-point EPnP up to
 // the null space of M^T M.  Lane 12g does the control points in registers, every lane builds one
@@ -616,30 +720,12 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnPObject* objs, int max_iters) 
 #pragma unroll
         for (int y = 0; y < 3; y++) m[3 * x + y] += pp[x] * pp[y];
     }
-    double dc[3], uct[9];
-    eig_sym_small<3>(m, dc, uct);
-#pragma unroll
-    for (int i = 1; i < 4; i++) {
-      const double k = sqrt(fmax(dc[i - 1], 0.0) / NP);
-#pragma unroll
-      for (int x = 0; x < 3; x++) cws[3 * i + x] = cws[x] + k * uct[3 * (i - 1) + x];
-    }
-    // compute_barycentric_coordinates
-    double cc[9], ci[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-      for (int x = 1; x < 4; x++) cc[3 * i + x - 1] = cws[3 * x + i] - cws[i];
-    pinv3(cc, ci);
+    double ci[9];
+    epnp_control_points(cws, m, NP, ci);
 #pragma unroll
     for (int i = 0; i < NP; i++) {
-      const double* pi = &pws[3 * i];
       double al[4];
-#pragma unroll
-      for (int x = 0; x < 3; x++)
-        al[1 + x] = ci[3 * x] * (pi[0] - cws[0]) + ci[3 * x + 1] * (pi[1] - cws[1]) +
-                    ci[3 * x + 2] * (pi[2] - cws[2]);
-      al[0] = 1.0f - al[1] - al[2] - al[3];
+      epnp_alphas(&pws[3 * i], cws, ci, al);
 #pragma unroll
       for (int x = 0; x < 4; x++) s_al[g][4 * i + x] = al[x];
     }
@@ -686,19 +772,7 @@ __global__ __launch_bounds__(64) void k_pnp_hyp(PnPObject* objs, int max_iters) 
   for (int e = j; e < 4 * NP; e += 12) rec[R_AL + e] = s_al[g][e];
   for (int e = j; e < 3 * NP; e += 12) rec[R_PW + e] = s_pws[g][e];
   if (j < 2 * NP) rec[R_US + j] = s_us[g][j];
-  if (j == 0) {
-    double L[60];
-    compute_L_6x10(s_ut[g], L);
-#pragma unroll
-    for (int i = 0; i < 60; i++) rec[R_L + i] = L[i];
-    const double* cws = s_cws[g];
-    rec[R_RHO + 0] = d_dist2(cws + 0, cws + 3);
-    rec[R_RHO + 1] = d_dist2(cws + 0, cws + 6);
-    rec[R_RHO + 2] = d_dist2(cws + 0, cws + 9);
-    rec[R_RHO + 3] = d_dist2(cws + 3, cws + 6);
-    rec[R_RHO + 4] = d_dist2(cws + 3, cws + 9);
-    rec[R_RHO + 5] = d_dist2(cws + 6, cws + 9);
-  }
+  if (j == 0) epnp_L_rho(s_ut[g], s_cws[g], rec);
 }
 
 // one lane per (hypothesis, object) for beta estimate V (betas_approx_V + gauss_newton +
@@ -710,36 +784,12 @@ __device__ __forceinline__ void pnp_beta(PnPObject& o, int max_iters) {
   if (h >= max_iters || n < NP) return;
   const double fu = o.fx, fv = o.fy, uc = o.cx, vc = o.cy;
   const double* rec = o.hrec + (size_t)kHypRec * h;
-  double L[60], rho[6], betas[4];
-#pragma unroll
-  for (int i = 0; i < 60; i++) L[i] = rec[R_L + i];
-#pragma unroll
-  for (int i = 0; i < 6; i++) rho[i] = rec[R_RHO + i];
-  if (V == 1)
-    betas_approx_1(L, rho, betas);
-  else if (V == 2)
-    betas_approx_2(L, rho, betas);
-  else
-    betas_approx_3(L, rho, betas);
-  gauss_newton(L, rho, betas);
   // compute_R_and_t: ccs, pcs, solve_for_sign, estimate_R_and_t, reprojection_error
   double ccs[12], pcs[3 * NP], pws[3 * NP], R[9], t[3];
+  epnp_ccs<V>(rec, ccs);
 #pragma unroll
-  for (int i = 0; i < 12; i++) ccs[i] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const double* v = rec + R_UT + 12 * (3 - i);  // ut row 11 - i
-#pragma unroll
-    for (int j = 0; j < 12; j++) ccs[j] += betas[i] * v[j];
-  }
-#pragma unroll
-  for (int i = 0; i < NP; i++) {
-    const double* a = rec + R_AL + 4 * i;
-#pragma unroll
-    for (int j = 0; j < 3; j++)
-      pcs[3 * i + j] = a[0] * ccs[j] + a[1] * ccs[3 + j] + a[2] * ccs[6 + j] + a[3] * ccs[9 + j];
-  }
-  if (pcs[2] < 0.0) {
+  for (int i = 0; i < NP; i++) epnp_pc(rec + R_AL + 4 * i, ccs, &pcs[3 * i]);
+  if (epnp_behind_camera(rec + R_AL, ccs)) {  // the test pcs[2] < 0 of solve_for_sign
 #pragma unroll
     for (int i = 0; i < 3 * NP; i++) pcs[i] = -pcs[i];
   }
@@ -770,19 +820,12 @@ __device__ __forceinline__ void pnp_beta(PnPObject& o, int max_iters) {
       abt[3 * j + 2] += (pc[j] - pc0[j]) * (pw[2] - pw0[2]);
     }
   }
-  procrustes_R(abt, R);
-#pragma unroll
-  for (int r = 0; r < 3; r++) t[r] = pc0[r] - d_dot3(R + 3 * r, pw0);
+  epnp_R_t(abt, pc0, pw0, R, t);
   double sum2 = 0.0;
 #pragma unroll
-  for (int i = 0; i < NP; i++) {
-    const double* pw = &pws[3 * i];
-    const double Xc = d_dot3(R, pw) + t[0], Yc = d_dot3(R + 3, pw) + t[1];
-    const double inv_Zc = 1.0 / (d_dot3(R + 6, pw) + t[2]);
-    const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
-    const double u = rec[R_US + 2 * i], v = rec[R_US + 2 * i + 1];
-    sum2 += sqrt((u - ue) * (u - ue) + (v - ve) * (v - ve));
-  }
+  for (int i = 0; i < NP; i++)
+    sum2 += epnp_reproj_dist(R, t, &pws[3 * i], rec[R_US + 2 * i], rec[R_US + 2 * i + 1], fu, fv,
+                             uc, vc);
   double* out = o.hout + (size_t)kHypOut * (3 * h + V - 1);
   out[0] = sum2 / NP;
 #pragma unroll
@@ -804,6 +847,32 @@ __global__ __launch_bounds__(64) void k_pnp_beta(PnPObject* objs, int max_iters)
     pnp_beta<3, NP>(o, max_iters);
 }
 
+// err, R, t of hypothesis h's chosen beta estimate
+__device__ __forceinline__ const double* pnp_chosen_estimate(const PnPObject& o, int h) {
+  const double* out = o.hout + (size_t)kHypOut * 3 * h;
+  return out + kHypOut * best_of_three(out[0], out[kHypOut], out[2 * kHypOut]);
+}
+
+// inlier mask (masks row `row`) and count of the points 0..n-1 under the predicate `inlier(i)`;
+// block-wide, 256 threads (s_w: one int per wave), the count returned to every thread
+template <typename Pred>
+__device__ __forceinline__ int wg_inlier_mask(PnPObject& o, int n, int row, int* s_w,
+                                              const Pred& inlier) {
+  int good = 0;
+  for (int i0 = 0; i0 < n; i0 += blockDim.x) {
+    const int i = i0 + threadIdx.x;
+    const bool in = i < n && inlier(i);
+    const unsigned long long bal = __ballot(in);
+    if ((threadIdx.x & 63) == 0 && i0 + (threadIdx.x & ~63) < n)
+      o.masks[(size_t)row * o.mask_words + (i0 + (threadIdx.x & ~63)) / 64] = bal;
+    good += in ? 1 : 0;
+  }
+  for (int off = 32; off > 0; off >>= 1) good += __shfl_xor(good, off, 64);
+  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = good;
+  __syncthreads();
+  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+}
+
 // one workgroup per (hypothesis, object): inlier count + mask (PnPRansacCallback::computeError,
 // RANSACPointSetRegistrator::findInliers with t = (float)(0.3 * 0.3))
 __global__ __launch_bounds__(256) void k_pnp_score(PnPObject* objs, int max_iters) {
@@ -815,13 +884,8 @@ __global__ __launch_bounds__(256) void k_pnp_score(PnPObject* objs, int max_iter
   if (h >= max_iters || n < 5) return;
   double* m = o.models + 6 * h;
   if (threadIdx.x == 0) {
-    // compute_pose's choice among the three beta estimates (rep_errors[2] < [1]; [3] < [N]),
-    // then the model as PnPRansacCallback stores it (rvec via Rodrigues, tvec)
-    const double* out = o.hout + (size_t)kHypOut * 3 * h;
-    int best = 0;
-    if (out[kHypOut] < out[0]) best = 1;
-    if (out[2 * kHypOut] < out[best * kHypOut]) best = 2;
-    const double* bo = out + best * kHypOut;
+    // the chosen estimate as PnPRansacCallback stores the model (rvec via Rodrigues, tvec)
+    const double* bo = pnp_chosen_estimate(o, h);
     double rv[3];
     d_rodrigues_r2v(bo + 1, rv);
     m[0] = rv[0];
@@ -835,36 +899,22 @@ __global__ __launch_bounds__(256) void k_pnp_score(PnPObject* objs, int max_iter
   __syncthreads();
   const double tx = m[3], ty = m[4], tz = m[5];
   const float thr = (float)(o.reproj * o.reproj);
-  const int words = (n + 63) / 64;
-  int good = 0;
-  for (int i0 = 0; i0 < n; i0 += blockDim.x) {
-    const int i = i0 + threadIdx.x;
-    bool in = false;
-    if (i < n) {
-      const double X = o.pts3[3 * i], Y = o.pts3[3 * i + 1], Z = o.pts3[3 * i + 2];
-      double x = sR[0] * X + sR[1] * Y + sR[2] * Z + tx;
-      double y = sR[3] * X + sR[4] * Y + sR[5] * Z + ty;
-      double z = sR[6] * X + sR[7] * Y + sR[8] * Z + tz;
-      z = z ? 1. / z : 1;
-      x *= z;
-      y *= z;
-      const float pu = (float)(x * (double)o.fx + (double)o.cx);
-      const float pv = (float)(y * (double)o.fy + (double)o.cy);
-      const float2 q = o.pts2[i];
-      const float du = q.x - pu, dv = q.y - pv;
-      // count == modelPoints: run() returns the model with every point marked inlier
-      in = n == 5 || (du * du + dv * dv) <= thr;
-    }
-    const unsigned long long bal = __ballot(in);
-    if ((threadIdx.x & 63) == 0 && i0 + (threadIdx.x & ~63) < n)
-      o.masks[(size_t)h * o.mask_words + (i0 + (threadIdx.x & ~63)) / 64] = bal;
-    good += in ? 1 : 0;
-  }
-  for (int off = 32; off > 0; off >>= 1) good += __shfl_xor(good, off, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = good;
-  __syncthreads();
-  if (threadIdx.x == 0) o.good[h] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-  (void)words;
+  const int good = wg_inlier_mask(o, n, h, s_w, [&](int i) {
+    const double X = o.pts3[3 * i], Y = o.pts3[3 * i + 1], Z = o.pts3[3 * i + 2];
+    double x = sR[0] * X + sR[1] * Y + sR[2] * Z + tx;
+    double y = sR[3] * X + sR[4] * Y + sR[5] * Z + ty;
+    double z = sR[6] * X + sR[7] * Y + sR[8] * Z + tz;
+    z = z ? 1. / z : 1;
+    x *= z;
+    y *= z;
+    const float pu = (float)(x * (double)o.fx + (double)o.cx);
+    const float pv = (float)(y * (double)o.fy + (double)o.cy);
+    const float2 q = o.pts2[i];
+    const float du = q.x - pu, dv = q.y - pv;
+    // count == modelPoints: run() returns the model with every point marked inlier
+    return n == 5 || (du * du + dv * dv) <= thr;
+  });
+  if (threadIdx.x == 0) o.good[h] = good;
 }
 
 __device__ int d_update_num_iters(double p, double ep, int model_points, int max_iters) {
@@ -945,24 +995,13 @@ __device__ __forceinline__ void refit_alphas(const PnPObject& o, int k, const do
                                              const double* ci, double* a) {
   double p[3];
   refit_pw(o, k, p);
-  for (int j = 0; j < 3; j++)
-    a[1 + j] = ci[3 * j] * (p[0] - cws[0]) + ci[3 * j + 1] * (p[1] - cws[1]) +
-               ci[3 * j + 2] * (p[2] - cws[2]);
-  a[0] = 1.0f - a[1] - a[2] - a[3];
+  epnp_alphas(p, cws, ci, a);
 }
 
 __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
   __shared__ RefitSmem S;
   PnPObject& o = objs[blockIdx.x];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#ifdef MMT_PNP_PROFILE
-  long long tp[8];
-  int np = 0;
-  if (tid == 0) tp[np++] = clock64();
-#define PNPPROF() do { if (tid == 0) tp[np++] = clock64(); } while (0)
-#else
-#define PNPPROF() do { } while (0)
-#endif
   const int best = o.result[0];
   if (best < 0) {
     if (tid == 0) o.result[3] = 0;
@@ -974,24 +1013,14 @@ __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
   for (int i0 = 0; i0 < n; i0 += blockDim.x) {
     const int i = i0 + tid;
     const bool in = i < n && ((mask[i >> 6] >> (i & 63)) & 1ull);
-    const unsigned long long bal = __ballot(in);
-    if (lane == 0) S.w[wave] = __popcll(bal);
-    __syncthreads();
-    int off = 0, tot = 0;
-    for (int w = 0; w < 4; w++) {
-      if (w < wave) off += S.w[w];
-      tot += S.w[w];
-    }
-    if (in) o.inliers[base + off + __popcll(bal & ((1ull << lane) - 1ull))] = i;
-    base += tot;
-    __syncthreads();
+    const int slot = wg_compact_slot<4>(in, S.w, base);
+    if (in) o.inliers[slot] = i;
   }
   if (tid == 0) {
     S.n = base;
     o.result[3] = base;
   }
   __syncthreads();
-  PNPPROF();
   const int ni = S.n;
   const double fu = o.fx, fv = o.fy, uc = o.cx, vc = o.cy;
   // control points: centroid, then PCA of the centred points
@@ -1020,23 +1049,12 @@ __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
     }
     wg_sum<9>(m, S.red, S.sum);
     if (tid == 0) {
-      double mm[9], dc[3], uct[9], cws[12], cc[9], ci[9];
+      double mm[9], cws[12], ci[9];
 #pragma unroll
       for (int i = 0; i < 9; i++) mm[i] = S.sum[i];
-      eig_sym_small<3>(mm, dc, uct);
 #pragma unroll
       for (int j = 0; j < 3; j++) cws[j] = S.cws[j];
-#pragma unroll
-      for (int i = 1; i < 4; i++) {
-        const double k = sqrt(fmax(dc[i - 1], 0.0) / ni);
-#pragma unroll
-        for (int j = 0; j < 3; j++) cws[3 * i + j] = cws[j] + k * uct[3 * (i - 1) + j];
-      }
-#pragma unroll
-      for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 1; j < 4; j++) cc[3 * i + j - 1] = cws[3 * j + i] - cws[i];
-      pinv3(cc, ci);
+      epnp_control_points(cws, mm, ni, ci);
 #pragma unroll
       for (int i = 0; i < 12; i++) S.cws[i] = cws[i];
 #pragma unroll
@@ -1044,7 +1062,6 @@ __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
     }
     __syncthreads();
   }
-  PNPPROF();
   // M^T M (upper triangle, 78 entries)
   {
     double v[78];
@@ -1078,7 +1095,6 @@ __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
     }
     __syncthreads();
   }
-  PNPPROF();
   if (wave == 0) {  // the eigen-solve runs on lanes 0..11 of wave 0
     const bool act = lane < 12;
     const int j = act ? lane : 0;
@@ -1089,74 +1105,30 @@ __global__ __launch_bounds__(256) void k_refit_null(PnPObject* objs) {
       v[k] = (act && k == j) ? 1.0 : 0.0;
     }
     int rank;
-    const int nsw = eig12_group(a, v, 0, act ? lane : 12 + (lane % 12), act, rank);
-#ifdef MMT_PNP_PROFILE
-    if (lane == 0) S.n = nsw;
-#else
-    (void)nsw;
-#endif
+    eig12_group(a, v, 0, act ? lane : 12 + (lane % 12), act, rank);
     if (act && rank >= 8)
 #pragma unroll
       for (int k = 0; k < 12; k++) S.ut8[(rank - 8) * 12 + k] = v[k];
   }
   __syncthreads();
-  PNPPROF();
   double* rec = o.hrec;
   for (int e = tid; e < 48; e += blockDim.x) rec[R_UT + e] = S.ut8[e];
   if (tid < 12) rec[R_AL + tid] = S.cws[tid];
   if (tid < 9) rec[R_PW + tid] = S.ci[tid];
-  if (tid == 0) {
-    double L[60];
-    compute_L_6x10(S.ut8, L);
-#pragma unroll
-    for (int i = 0; i < 60; i++) rec[R_L + i] = L[i];
-    const double* cws = S.cws;
-    rec[R_RHO + 0] = d_dist2(cws + 0, cws + 3);
-    rec[R_RHO + 1] = d_dist2(cws + 0, cws + 6);
-    rec[R_RHO + 2] = d_dist2(cws + 0, cws + 9);
-    rec[R_RHO + 3] = d_dist2(cws + 3, cws + 6);
-    rec[R_RHO + 4] = d_dist2(cws + 3, cws + 9);
-    rec[R_RHO + 5] = d_dist2(cws + 6, cws + 9);
-  }
-#ifdef MMT_PNP_PROFILE
-  if (tid == 0)
-    printf("refitprof ni=%d compact=%lld ctrl=%lld mtm=%lld eig=%lld sweeps=%d\n", ni,
-           tp[1] - tp[0], tp[2] - tp[1], tp[3] - tp[2], tp[4] - tp[3], S.n);
-#endif
-#undef PNPPROF
+  if (tid == 0) epnp_L_rho(S.ut8, S.cws, rec);
 }
 
 template <int V>
 __device__ __forceinline__ void refit_beta(PnPObject& o) {
   if (threadIdx.x != 0 || o.result[0] < 0) return;
   const double* rec = o.hrec;
-  double L[60], rho[6], betas[4], ccs[12];
-#pragma unroll
-  for (int i = 0; i < 60; i++) L[i] = rec[R_L + i];
-#pragma unroll
-  for (int i = 0; i < 6; i++) rho[i] = rec[R_RHO + i];
-  if (V == 1)
-    betas_approx_1(L, rho, betas);
-  else if (V == 2)
-    betas_approx_2(L, rho, betas);
-  else
-    betas_approx_3(L, rho, betas);
-  gauss_newton(L, rho, betas);
-#pragma unroll
-  for (int i = 0; i < 12; i++) ccs[i] = 0.0f;
-#pragma unroll
-  for (int i = 0; i < 4; i++) {
-    const double* v = rec + R_UT + 12 * (3 - i);  // ut row 11 - i
-#pragma unroll
-    for (int j = 0; j < 12; j++) ccs[j] += betas[i] * v[j];
-  }
-  // solve_for_sign on the first inlier's camera depth
-  double a[4];
-  refit_alphas(o, 0, rec + R_AL, rec + R_PW, a);
-  const double pc2 = a[0] * ccs[2] + a[1] * ccs[5] + a[2] * ccs[8] + a[3] * ccs[11];
+  double ccs[12], a[4];
+  epnp_ccs<V>(rec, ccs);
+  refit_alphas(o, 0, rec + R_AL, rec + R_PW, a);  // the first inlier's
+  const bool flip = epnp_behind_camera(a, ccs);
   double* out = o.hout + (size_t)kHypOut * (V - 1);
 #pragma unroll
-  for (int i = 0; i < 12; i++) out[i] = pc2 < 0.0 ? -ccs[i] : ccs[i];
+  for (int i = 0; i < 12; i++) out[i] = flip ? -ccs[i] : ccs[i];
 }
 
 __global__ __launch_bounds__(64) void k_refit_beta(PnPObject* objs) {
@@ -1194,8 +1166,7 @@ __global__ __launch_bounds__(256) void k_refit_rt(PnPObject* objs) {
   auto pcs = [&](int k, int var, double* pc) {
     double a[4];
     refit_alphas(o, k, S.cws, S.ci, a);
-    const double* c = S.ccs + 12 * var;
-    for (int j = 0; j < 3; j++) pc[j] = a[0] * c[j] + a[1] * c[3 + j] + a[2] * c[6 + j] + a[3] * c[9 + j];
+    epnp_pc(a, S.ccs + 12 * var, pc);
   };
   {  // centroids of the three camera-frame point sets and of the world points
     double v[12];
@@ -1242,11 +1213,9 @@ __global__ __launch_bounds__(256) void k_refit_rt(PnPObject* objs) {
       double abt[9], R[9];
 #pragma unroll
       for (int i = 0; i < 9; i++) abt[i] = S.sum[9 * wave + i];
-      procrustes_R(abt, R);
+      epnp_R_t(abt, S.pc0 + 3 * wave, S.pw0, R, S.t + 3 * wave);
 #pragma unroll
       for (int i = 0; i < 9; i++) S.R[9 * wave + i] = R[i];
-#pragma unroll
-      for (int r = 0; r < 3; r++) S.t[3 * wave + r] = S.pc0[3 * wave + r] - d_dot3(R + 3 * r, S.pw0);
     }
     __syncthreads();
   }
@@ -1257,20 +1226,12 @@ __global__ __launch_bounds__(256) void k_refit_rt(PnPObject* objs) {
       refit_pw(o, k, p);
       refit_us(o, k, u, vv);
 #pragma unroll
-      for (int var = 0; var < 3; var++) {
-        const double* R = S.R + 9 * var;
-        const double* t = S.t + 3 * var;
-        const double Xc = d_dot3(R, p) + t[0], Yc = d_dot3(R + 3, p) + t[1];
-        const double inv_Zc = 1.0 / (d_dot3(R + 6, p) + t[2]);
-        const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
-        v[var] += sqrt((u - ue) * (u - ue) + (vv - ve) * (vv - ve));
-      }
+      for (int var = 0; var < 3; var++)
+        v[var] += epnp_reproj_dist(S.R + 9 * var, S.t + 3 * var, p, u, vv, fu, fv, uc, vc);
     }
     wg_sum<3>(v, S.red, S.sum);
     if (tid == 0) {
-      int best = 0;
-      if (S.sum[1] / ni < S.sum[0] / ni) best = 1;
-      if (S.sum[2] / ni < S.sum[best] / ni) best = 2;
+      const int best = best_of_three(S.sum[0] / ni, S.sum[1] / ni, S.sum[2] / ni);
       double rv[3], R[9];
       if (o.rt_raw) {  // D6: compute_pose's R as it is (no Rodrigues round trip)
         for (int i = 0; i < 9; i++) R[i] = S.R[9 * best + i];
@@ -1282,16 +1243,6 @@ __global__ __launch_bounds__(256) void k_refit_rt(PnPObject* objs) {
       for (int i = 0; i < 3; i++) o.Rt[9 + i] = S.t[3 * best + i];
     }
   }
-}
-
-// motion-model inliers (pnp_mm_inliers_block, mmt_pnp.h), one workgroup per object
-__global__ __launch_bounds__(256) void k_mm_inliers(PnPObject* objs) {
-  pnp_mm_inliers_block(objs[blockIdx.x]);
-}
-
-// D3 edge index list (pnp_subset_block, mmt_pnp.h), one workgroup per object
-__global__ __launch_bounds__(256) void k_pnp_subset(PnPObject* objs) {
-  pnp_subset_block(objs[blockIdx.x]);
 }
 
 // ---------------------------------------------------------------- D6: PnPsolver (P4P RANSAC)
@@ -1314,24 +1265,10 @@ __device__ __forceinline__ bool p4p_inlier(const PnPObject& o, const double* R, 
 
 // inlier count + mask of pose (R, t) into masks row `row`; block-wide, 256 threads
 __device__ int p4p_check(PnPObject& o, const double* R, const double* t, int row, int* s_w) {
-  const int n = *o.n;
-  int good = 0;
-  for (int i0 = 0; i0 < n; i0 += blockDim.x) {
-    const int i = i0 + threadIdx.x;
-    const bool in = i < n && p4p_inlier(o, R, t, i);
-    const unsigned long long bal = __ballot(in);
-    if ((threadIdx.x & 63) == 0 && i0 + (threadIdx.x & ~63) < n)
-      o.masks[(size_t)row * o.mask_words + (i0 + (threadIdx.x & ~63)) / 64] = bal;
-    good += in ? 1 : 0;
-  }
-  for (int off = 32; off > 0; off >>= 1) good += __shfl_xor(good, off, 64);
-  if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = good;
-  __syncthreads();
-  return s_w[0] + s_w[1] + s_w[2] + s_w[3];
+  return wg_inlier_mask(o, *o.n, row, s_w, [&](int i) { return p4p_inlier(o, R, t, i); });
 }
 
-// one workgroup per hypothesis: compute_pose's choice among the three beta estimates
-// (rep_errors[2] < [1]; [3] < [N]), then CheckInliers
+// one workgroup per hypothesis: its chosen estimate, then CheckInliers
 __global__ __launch_bounds__(256) void k_p4p_check(PnPObject* objs, int K) {
   __shared__ double sRt[12];
   __shared__ int s_w[4];
@@ -1339,11 +1276,7 @@ __global__ __launch_bounds__(256) void k_p4p_check(PnPObject* objs, int K) {
   const int h = blockIdx.x;
   if (h >= K || *o.n < 4) return;
   if (threadIdx.x == 0) {
-    const double* out = o.hout + (size_t)kHypOut * 3 * h;
-    int best = 0;
-    if (out[kHypOut] < out[0]) best = 1;
-    if (out[2 * kHypOut] < out[best * kHypOut]) best = 2;
-    const double* bo = out + best * kHypOut;
+    const double* bo = pnp_chosen_estimate(o, h);
     for (int i = 0; i < 12; i++) {
       sRt[i] = bo[1 + i];
       o.hrt[12 * h + i] = bo[1 + i];
@@ -1556,14 +1489,6 @@ void launch_pnp(PnPObject* d_objs, int nobj, int max_iters, hipStream_t st, bool
   hipLaunchKernelGGL(k_refit_null, dim3(nobj), dim3(256), 0, st, d_objs);
   hipLaunchKernelGGL(k_refit_beta, dim3(nobj, 3), dim3(64), 0, st, d_objs);
   hipLaunchKernelGGL(k_refit_rt, dim3(nobj), dim3(256), 0, st, d_objs);
-}
-
-void launch_pnp_mm(PnPObject* d_objs, int nobj, hipStream_t st) {
-  hipLaunchKernelGGL(k_mm_inliers, dim3(nobj), dim3(256), 0, st, d_objs);
-}
-
-void launch_pnp_subset(PnPObject* d_objs, int nobj, hipStream_t st) {
-  hipLaunchKernelGGL(k_pnp_subset, dim3(nobj), dim3(256), 0, st, d_objs);
 }
 
 }  // namespace mmt

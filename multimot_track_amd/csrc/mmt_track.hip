@@ -15,6 +15,7 @@
 #include "mmt_devmath.h"
 #include "mmt_internal.h"
 #include "mmt_track.h"
+#include "mmt_wgscan.h"
 
 namespace mmt {
 
@@ -55,33 +56,12 @@ __global__ __launch_bounds__(256) void k_gray_depth(const uint8_t* __restrict__ 
   if (p < npix) gray_depth_px(B + 3 * (size_t)p, D[p], bf, G + p, Z + p);
 }
 
-// order-preserving workgroup compaction helper: returns this lane's slot (or -1) and advances
-// `base` by the round's total.  blockDim = 1024.
-__device__ __forceinline__ int wg_compact_slot(bool keep, int* s_w, int& base) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  const unsigned long long bal = __ballot(keep);
-  if (lane == 0) s_w[wave] = __popcll(bal);
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < nw; w++) {
-    const int c = s_w[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  const int slot = keep ? base + off + __popcll(bal & ((1ull << lane) - 1ull)) : -1;
-  base += tot;
-  __syncthreads();
-  return slot;
-}
-
 // B2 (+ mvSiftDepthTmp) for one frame; single workgroup of 1024 threads.  Each thread takes up to
 // kSsItems consecutive keys per round and issues all their key loads, then all their depth, label
 // and flow gathers, before anything waits: two memory round trips per round (a key count up to
 // 4,096 is one round), not three per 1,024 keys.  The flow is gathered for every key and used
 // only where the label and depth keep it.
 constexpr int kSsItems = 4;
-
-__device__ __forceinline__ int block_scan_excl(int v, int* s_w, int& excl);
 
 __global__ __launch_bounds__(1024) void k_static_samples(const mmt_kp* __restrict__ kps,
                                                          const int* __restrict__ nkp,
@@ -143,29 +123,6 @@ __global__ __launch_bounds__(1024) void k_static_samples(const mmt_kp* __restric
     base += tot;
   }
   if (threadIdx.x == 0) *out.count = min(base, out.cap);
-}
-
-// B1 for one frame; single workgroup, grid positions in row-major order.
-// exclusive block-wide scan of one int per thread (thread order); returns the total
-__device__ __forceinline__ int block_scan_excl(int v, int* s_w, int& excl) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int y = __shfl_up(x, o, 64);
-    if (lane >= o) x += y;
-  }
-  if (lane == 63) s_w[wave] = x;
-  __syncthreads();
-  int off = 0, tot = 0;
-  for (int w = 0; w < nw; w++) {
-    const int c = s_w[w];
-    if (w < wave) off += c;
-    tot += c;
-  }
-  excl = off + x - v;
-  __syncthreads();
-  return tot;
 }
 
 // B1: every 4th row/column, order-preserving, over kObjBlocks workgroups (one CU cannot pull the
@@ -235,7 +192,7 @@ __global__ __launch_bounds__(256) void k_obj_write(const float* __restrict__ dep
     float d = 0;
     float2 fl = make_float2(0.f, 0.f);
     const bool keep = g < g1 && obj_keep(depth, flow, mask, W, H, gw, g, lab, d, fl);
-    const int slot = wg_compact_slot(keep, s_w, base);
+    const int slot = wg_compact_slot<4>(keep, s_w, base);  // launched with 256 threads
     if (keep && slot < out.cap) {
       const int i = (g / gw) * 4, j = (g % gw) * 4;
       out.keys[slot] = make_float2((float)j, (float)i);

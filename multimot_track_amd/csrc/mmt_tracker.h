@@ -49,12 +49,9 @@ struct MMPrepArgs {
   const int* prevStats;    // previous frame's D3 stats (3 per object)
   float TcwPrev[16], TcwCur[16];
 };
-void launch_obj_mm_prep(const MMPrepArgs& a, hipStream_t st);
-// the four kernels of stage B (motion-model matrix and inliers, model choice, D3 edge list) as
-// one launch, one workgroup per object
+// stage B (motion-model matrix and inliers, model choice, D3 edge list) in one launch, one
+// workgroup per object
 void launch_obj_stage_b(const MMPrepArgs& a, FlowSolveDesc* descs, float* init, hipStream_t st);
-void launch_obj_model_choice(PnPObject* objs, int nobj, FlowSolveDesc* descs, float* init,
-                             hipStream_t st);
 // RANSACPointSetRegistrator::getSubset draws (5-point subsets) for a point count.
 void ransac_subsets(int count, int iters, std::vector<int>& idx);
 

@@ -25,6 +25,7 @@
 #include "mmt_pnp.h"
 #include "mmt_track.h"
 #include "mmt_tracker.h"
+#include "mmt_wgscan.h"
 
 namespace mmt {
 
@@ -972,7 +973,7 @@ void Tracker::obj_stage_b(ObjFrame& F) {
   ObjHost& H = *oh_[q];
   // behind this frame's RANSAC (oa_) by an event, behind the previous frame's D3 (whose motions
   // the motion model needs) by the stream
-  // D3 descriptors; the initial motion is the device's model choice (k_obj_model_choice)
+  // D3 descriptors; the initial motion is the device's model choice (k_obj_stage_b)
   for (int i = 0; i < nobj; i++) {
     FlowSolveDesc& d = H.descs[i];
     memset(&d, 0, sizeof(d));
@@ -1062,55 +1063,17 @@ void Tracker::obj_finish(ObjFrame& F) {
 }
 
 // ---------------------------------------------------------------- device side of stage B
-__global__ void k_obj_mm_prep(MMPrepArgs a) {
-  const int i = threadIdx.x;
-  if (i >= a.nobj || a.pre[i] < 0) return;
-  const int p = a.pre[i];
-  float X[16], Ti[16], vobj[16], MM[16];
-  if (a.prevStats[3 * p + 2] != 0)
-    mat4_eye(X);
-  else
-    for (int k = 0; k < 16; k++) X[k] = a.prevX[16 * p + k];
-  inv_mat(a.TcwPrev, Ti);
-  mat4_mul(Ti, X, vobj);  // the previous frame's vObjMod[p] (its finish computes the same)
-  mat4_mul(a.TcwCur, vobj, MM);
-  for (int k = 0; k < 16; k++) a.objs[i].MM[k] = MM[k];
-}
-
-// GetInitModelObj's choice (Tracking.cc:4400-4420): the RANSAC model unless the motion model has
-// at least as many inliers; the chosen motion seeds D3
-__global__ void k_obj_model_choice(PnPObject* objs, int nobj, FlowSolveDesc* descs, float* init) {
-  const int i = threadIdx.x;
-  if (i >= nobj) return;
-  PnPObject& o = objs[i];
-  const int n_ransac = o.result[0] >= 0 ? o.result[3] : 0;
-  const int n_mm = o.use_mm ? o.result[4] : -1;
-  float Mod[16];
-  mat4_eye(Mod);
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) Mod[4 * r + c] = (float)o.Rt[3 * r + c];
-    Mod[4 * r + 3] = (float)o.Rt[9 + r];
-  }
-  const bool choice = o.use_mm && !(n_ransac > n_mm);
-  o.use_mm_choice = choice ? 1 : 0;
-  for (int k = 0; k < 16; k++) {
-    const float v = choice ? o.MM[k] : Mod[k];
-    descs[i].init[k] = v;
-    init[16 * i + k] = v;
-  }
-}
-
 // Stage B of one frame's objects in one launch (one workgroup per object; the objects are
-// independent): the motion-model matrix (k_obj_mm_prep), its inliers (pnp_mm_inliers_block), the
-// model choice that seeds D3 (k_obj_model_choice) and D3's edge list (pnp_subset_block) -- the
-// same results as the four separate kernels, without three dependent launches on the critical
-// chain.
+// independent), so the critical chain into D3 holds no dependent launches between them: the
+// motion-model matrix MM = Tcw * vObjMod[PreObjID], its inliers in ascending order
+// (GetInitModelObj, Tracking.cc:4380-4399), the choice between the RANSAC model and the motion
+// model that seeds D3 (Tracking.cc:4400-4420: the RANSAC model unless the motion model has at
+// least as many inliers) and D3's edge list ObjId_sub[i] = ObjId[inliers[i]] of the chosen model.
 __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc* descs,
                                                      float* init) {
   __shared__ float s_MM[16];
   __shared__ int s_w[4];
   const int i = blockIdx.x, tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
   PnPObject& o = a.objs[i];
   // Everything this launch reads but does not write is loaded up front, so the dependent global
   // round trips on the critical D3 chain are the motion-model matrix and the inlier lists only.
@@ -1126,14 +1089,14 @@ __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc
   const int* res = o.result;
   const int res3 = res[3];
   const int n_ransac = res[0] >= 0 ? res3 : 0;
-  if (tid == 0 && a.pre[i] >= 0) {  // MM = Tcw * vObjMod[PreObjID] (k_obj_mm_prep)
+  if (tid == 0 && a.pre[i] >= 0) {  // MM = Tcw * vObjMod[PreObjID]
     const int p = a.pre[i];
     float X[16], Ti[16], vobj[16], MM[16];
     const int fail = a.prevStats[3 * p + 2];
     for (int k = 0; k < 16; k++) X[k] = a.prevX[16 * p + k];
     if (fail != 0) mat4_eye(X);
     inv_mat(a.TcwPrev, Ti);
-    mat4_mul(Ti, X, vobj);
+    mat4_mul(Ti, X, vobj);  // the previous frame's vObjMod[p] (its finish computes the same)
     mat4_mul(a.TcwCur, vobj, MM);
     for (int k = 0; k < 16; k++) {
       o.MM[k] = MM[k];
@@ -1141,7 +1104,7 @@ __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc
     }
   }
   __syncthreads();
-  // motion-model inliers, ascending (pnp_mm_inliers_block with the matrix from LDS)
+  // motion-model inliers, ascending, with the matrix from LDS
   int n_mm = -1;
   if (use_mm) {
     float MM[16];
@@ -1165,21 +1128,12 @@ __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc
         const float Rpe = sqrtf(u_ * u_ + v_ * v_);
         in = (double)Rpe < reproj;
       }
-      const unsigned long long bal = __ballot(in);
-      if (lane == 0) s_w[wave] = __popcll(bal);
-      __syncthreads();
-      int off = 0, tot = 0;
-      for (int w = 0; w < 4; w++) {
-        if (w < wave) off += s_w[w];
-        tot += s_w[w];
-      }
-      if (in) mm_inliers[base + off + __popcll(bal & ((1ull << lane) - 1ull))] = j;
-      base += tot;
-      __syncthreads();
+      const int slot = wg_compact_slot<4>(in, s_w, base);
+      if (in) mm_inliers[slot] = j;
     }
     n_mm = base;
   }
-  // model choice (k_obj_model_choice), the same in every thread
+  // model choice, the same in every thread
   const bool choice = use_mm && !(n_ransac > n_mm);
   if (tid == 0) {
     if (use_mm) o.result[4] = n_mm;
@@ -1199,8 +1153,8 @@ __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc
       init[16 * i + k] = Mod[k];
     }
   }
-  // D3 edge list (pnp_subset_block): the chosen model's inliers as sample indices; the motion-model
-  // list was completed before the inlier loop's last barrier
+  // D3 edge list: the chosen model's inliers as sample indices; the motion-model list was
+  // completed before the inlier loop's last barrier
   const int n_sub = choice ? n_mm : res3;
   const int* src = choice ? mm_inliers : rs_inliers;
   int* sub = o.subset;
@@ -1210,15 +1164,6 @@ __global__ __launch_bounds__(256) void k_obj_stage_b(MMPrepArgs a, FlowSolveDesc
 
 void launch_obj_stage_b(const MMPrepArgs& a, FlowSolveDesc* descs, float* init, hipStream_t st) {
   hipLaunchKernelGGL(k_obj_stage_b, dim3(a.nobj), dim3(256), 0, st, a, descs, init);
-}
-
-void launch_obj_mm_prep(const MMPrepArgs& a, hipStream_t st) {
-  hipLaunchKernelGGL(k_obj_mm_prep, dim3(1), dim3(64), 0, st, a);
-}
-
-void launch_obj_model_choice(PnPObject* objs, int nobj, FlowSolveDesc* descs, float* init,
-                             hipStream_t st) {
-  hipLaunchKernelGGL(k_obj_model_choice, dim3(1), dim3(64), 0, st, objs, nobj, descs, init);
 }
 
 }  // namespace mmt

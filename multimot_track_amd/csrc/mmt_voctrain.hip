@@ -33,6 +33,7 @@
 #include "mmt_devbuf.h"
 #include "mmt_internal.h"
 #include "mmt_voctrain.h"
+#include "mmt_wgscan.h"
 
 namespace mmt {
 
@@ -103,15 +104,6 @@ __global__ __launch_bounds__(256) void k_seed_dist(const VtItem* __restrict__ it
   if (threadIdx.x == 0) item_sum[blockIdx.x] = s_part[0] + s_part[1] + s_part[2] + s_part[3];
 }
 
-// inclusive scan of v over the wave
-__device__ __forceinline__ uint32_t wave_scan(uint32_t v, int lane) {
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t u = __shfl_up(v, o);
-    if (lane >= o) v += u;
-  }
-  return v;
-}
-
 // One wave per node, round r >= 1: dist_sum, cut_d = RandomValue(0, dist_sum) from the uploaded
 // draw, and the first feature with d_up_now >= cut_d.  The sums are integers, so d_up_now >= cut_d
 // is d_up_now >= ceil(cut_d).
@@ -141,7 +133,7 @@ __global__ __launch_bounds__(64) void k_seed_pick(const VtNode* __restrict__ nod
   bool found = false;
   for (int b = 0; b < nd.n_items && !found; b += 64) {
     const uint32_t v = b + lane < nd.n_items ? item_sum[nd.item0 + b + lane] : 0u;
-    const uint32_t inc = wave_scan(v, lane);
+    const uint32_t inc = wave_scan_incl(v);
     const unsigned long long hit = __ballot(run + inc >= target);
     if (hit) {
       const int l = __ffsll((long long)hit) - 1;
@@ -161,7 +153,7 @@ __global__ __launch_bounds__(64) void k_seed_pick(const VtNode* __restrict__ nod
   bool got = false;
   for (int b = 0; b < it.count && !got && found; b += 64) {
     const uint32_t v = b + lane < it.count ? min_dist[it.begin + b + lane] : 0u;
-    const uint32_t inc = wave_scan(v, lane);
+    const uint32_t inc = wave_scan_incl(v);
     const unsigned long long hit = __ballot(b + lane < it.count && run + inc >= target);
     if (hit) {
       pos = it.begin + b + __ffsll((long long)hit) - 1;
